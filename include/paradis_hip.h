@@ -341,6 +341,21 @@ int paradis_adamw_multi(const int64_t* ptrs, const int64_t* numel, const int* ch
                         float beta2, float eps, float weight_decay, int step, const int* dev_state, void* stream);
 int paradis_adamw_tick(int* dev_state, void* stream);
 
+/* ---- f1 (AMSE): the spectral loss of reference utils/amse_loss.py on the equiangular grid H x W, W = 2(H-1), poles
+ * included; row j of a plane is colatitude pi*j/(H-1) (RealSHT's order).  M = H-1 degrees / orders are used.
+ * Tables (built once per grid and device): leg = paradis_amse_table_floats(H) floats, the quadrature-weighted
+ * orthonormal Legendre functions times sqrt(4 pi) (fp64 recurrence, stored fp32) for l >= m, l < M; twiddle = W*2*(H-1)
+ * floats; ws = paradis_amse_tables_ws_bytes(H) bytes of scratch. */
+size_t paradis_amse_table_floats(int H);
+size_t paradis_amse_tables_ws_bytes(int H);
+int paradis_amse_tables(float* leg, float* twiddle, double* ws, int H, int W, void* stream);
+/* loss[0] = AMSE(pred, target) over N = B*C planes [N,H,W] (mean over scales k < H-1, then over the planes); a NaN
+ * result becomes 1e6 on the device.  grad (NULL to skip) = d loss / d pred for upstream gradient 1, all zero when the
+ * value was NaN.  ws: paradis_amse_ws_bytes(N, H) bytes.  Fixed-order reductions: bit-reproducible. */
+size_t paradis_amse_ws_bytes(int N, int H);
+int paradis_amse_loss(const float* pred, const float* target, const float* leg, const float* twiddle, float* loss,
+                      float* grad, void* ws, int N, int H, int W, void* stream);
+
 /* ---- f3 (second half): Muon / NorMuon step on T same-shaped weight matrices w_t[rows, cols] (conv
  * weights flattened to [out, in*kh*kw]), the reference's default optimiser for Conv/Linear weights
  * (trainer.py:24-64,337-364; `dion` package, un-vendored and un-pinned: restated from its published

@@ -101,6 +101,11 @@ SIGNATURES = {
     "paradis_adamw_chunk": (I, []),
     "paradis_adamw_multi": (I, [P, P, P, P, I, I, F, F, F, F, F, I, P, P]),
     "paradis_adamw_tick": (I, [P, P]),
+    "paradis_amse_table_floats": (S, [I]),
+    "paradis_amse_tables_ws_bytes": (S, [I]),
+    "paradis_amse_tables": (I, [P, P, P, I, I, P]),
+    "paradis_amse_ws_bytes": (S, [I, I]),
+    "paradis_amse_loss": (I, [P, P, P, P, P, P, P, I, I, I, P]),
 }
 
 _missing = []

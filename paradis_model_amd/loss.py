@@ -5,6 +5,10 @@ blocks-of-``num_levels`` walk over the first ``num_features-num_surface_vars`` c
 On the HIP device ``forward`` is ONE fused kernel (``paradis_loss_fwd_bwd``: weighted loss value and
 d loss / d pred in a single pass over pred/target); on CPU tensors (weight construction tests, the
 gloo harness test) it is the plain elementwise formula.
+
+``"amse"`` is the reference's spectral loss (utils/amse_loss.py, wired in at utils/loss.py:90-99): ``ops.amse_loss``, the
+HIP spherical-harmonic transforms of sht.hip, on the equiangular grid of ``lat_grid`` (nlon = 2*(nlat-1)); latitude
+weights are switched off, and the scalar AMSE is multiplied by the feature weights afterwards, as the reference does.
 """
 import re
 
@@ -17,7 +21,7 @@ class ParadisLoss(torch.nn.Module):
                  output_name_order: list, delta_loss: float = 1.0,
                  apply_latitude_weights: bool = False) -> None:
         super().__init__()
-        if loss_function not in ("mse", "reversed_huber"):
+        if loss_function not in ("mse", "reversed_huber", "amse"):
             raise Exception(f"{loss_function} not supported, choose between [reversed_huber, mse]")
         self.kind = loss_function
         self.pressure_levels = pressure_levels.to(torch.float32)
@@ -34,6 +38,11 @@ class ParadisLoss(torch.nn.Module):
         self.feature_weights = self._feature_weights()
         self.register_buffer("feature_weights_buf", self.feature_weights.view(1, -1, 1, 1),
                              persistent=False)
+        if loss_function == "amse":
+            # reference utils/loss.py:93-99: AMSELoss(nlat=len(lat_grid), nlon=2*(len(lat_grid)-1), "equiangular"),
+            # latitude weights deactivated
+            self.nlat, self.nlon = len(lat_grid), 2 * (len(lat_grid) - 1)
+            self.apply_latitude_weights = False
 
     @staticmethod
     def _latitude_weights(lat_deg: torch.Tensor) -> torch.Tensor:
@@ -68,7 +77,17 @@ class ParadisLoss(torch.nn.Module):
     # The two methods below are the reference's per-variable validation metric (utils/loss.py:105-127): a [C] vector for
     # logging, off the training hot path, a handful of ATen elementwise ops on whatever device the tensors live on.
     # The training loss itself (forward) has one implementation only, the fused HIP kernel.
+    def _amse(self, pred, target):
+        from . import ops
+        if pred.shape[-2:] != (self.nlat, self.nlon):
+            ops.amse_grid_check(pred.shape[-2], pred.shape[-1])
+            raise ValueError(f"amse: the loss was built for a {self.nlat}x{self.nlon} grid, got "
+                             f"{pred.shape[-2]}x{pred.shape[-1]}")
+        return ops.amse_loss(pred, target)
+
     def _pointwise_loss(self, pred, target):
+        if self.kind == "amse":       # a scalar: the reference's per-channel metric is then amse * feature weight
+            return self._amse(pred, target)
         if self.kind == "mse":
             return (pred - target) ** 2
         d = self.delta
@@ -89,12 +108,15 @@ class ParadisLoss(torch.nn.Module):
         """Fused HIP kernel (value and d/dpred in one pass); like every module of this package it refuses CPU tensors -
         the CPU evaluation of the loss is ``oracle.paradis_oracle.paradis_loss`` (tests only)."""
         from . import ops
+        if self.kind == "amse":       # reference utils/loss.py:271-282 on a scalar loss: amse * mean(feature weights)
+            return (self._amse(pred, target) * self.feature_weights_buf).mean()
         lw = self.lat_weights_buf.reshape(-1) if self.apply_latitude_weights else None
         return ops.paradis_loss(pred, target, self.feature_weights_buf.reshape(-1), lw, self.kind, self.delta)
 
 
-def build_loss(cfg, lat_deg: torch.Tensor) -> ParadisLoss:
-    """Loss-weight assembly of reference ``trainer.py:112-187`` from the config."""
+def build_loss(cfg, lat_deg: torch.Tensor, loss_type: str = None) -> ParadisLoss:
+    """Loss-weight assembly of reference ``trainer.py:112-187`` from the config (``loss_type``: another loss type with the
+    same weights, the validation loss of ``build_val_loss``)."""
     from .config import feature_layout
     lay = feature_layout(cfg)
     vw = cfg.training.variable_loss_weights
@@ -108,10 +130,21 @@ def build_loss(cfg, lat_deg: torch.Tensor) -> ParadisLoss:
         else:
             raise ValueError(f"No loss weight configured for output feature '{feat}' "
                              f"(base variable '{base}').")
-    return ParadisLoss(loss_function=cfg.training.loss_function.type, lat_grid=lat_deg,
+    return ParadisLoss(loss_function=loss_type if loss_type is not None else cfg.training.loss_function.type,
+                       lat_grid=lat_deg,
                        pressure_levels=torch.tensor(cfg.features.pressure_levels, dtype=torch.float32),
                        num_features=lay.num_out_features,
                        num_surface_vars=len(cfg.features.output.surface), var_loss_weights=weights,
                        output_name_order=lay.output_name_order,
                        delta_loss=cfg.training.loss_function.delta_loss,
                        apply_latitude_weights=cfg.training.loss_function.lat_weights)
+
+
+def build_val_loss(cfg, lat_deg: torch.Tensor, train_loss: ParadisLoss = None) -> ParadisLoss:
+    """Validation loss of reference ``trainer.py:189-210``: ``training.loss_function.validation_loss`` when it is set (same
+    weights, same delta and latitude-weight switch), otherwise the training loss itself (``train_loss`` when given, else
+    the one ``build_loss`` makes)."""
+    vtype = cfg.training.loss_function.get("validation_loss", None)
+    if vtype is not None:
+        return build_loss(cfg, lat_deg, vtype)
+    return train_loss if train_loss is not None else build_loss(cfg, lat_deg)
