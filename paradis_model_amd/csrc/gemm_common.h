@@ -1,0 +1,787 @@
+// What the three translation units of the pointwise GEMMs share: gemm.hip (the fp32-width schemes and the C ABI),
+// gemm_amp_fwd.hip and gemm_amp_wgrad.hip (the bf16-mixed scheme's forward / data-gradient and weight-gradient kernels).
+// Arguments, tile constants, the epilogue, the split / round helpers, the one kernel template that two units instantiate
+// (pw_gemm_wgrad_split_kernel) and the launch helpers.  Everything below the declarations sits in an anonymous namespace.
+#pragma once
+#include <initializer_list>
+#include "common.h"
+
+struct GemmArgs {
+  const float* A; const float* B; float* C;
+  int M, N, K;
+  int64_t lda, ldb, ldc;
+  int64_t a_bs, b_bs, c_bs;   // stride between grid batches (fwd/dgrad: sample; wgrad: split slab)
+  int nbatch;                 // grid batches (fwd/dgrad: samples; wgrad: k-range splits)
+  int inner;                  // wgrad: number of samples reduced (0 for fwd/dgrad)
+  int64_t a_is, b_is;         // wgrad: strides between samples
+  // epilogue:  v = acc (+bias[m]) (+map[m,n]); zout = v; v = zmul ? v*act'(zmul) : act(v);
+  //            v = gate ? res + sigmoid(gate[m]) (v - res) : v + res
+  const float* bias; const float* map; const float* res; const float* zmul; float* zout;
+  const float* gate;          // [M] or NULL: the residual is blended in per output channel (gated blend of the advection)
+  int64_t res_bs, zmul_bs, zout_bs;
+  int act;
+  int stagger;                // start-up skew between co-resident workgroups, in units of 512 cycles
+  float* rowsum;              // wgrad only: [nbatch][M] partial row sums of A (= bias gradient), or NULL
+  // low-rank bias map applied on the fly: acc[m,n] += sum_c pw[c*M + m] * m8[c*N + n]  (M % 4 == 0)
+  const float* m8; const float* pw; int cin;
+  // f16x2 scheme: where the operands' max |value| comes from.  a_amax: one word (bits of max |A|, weight
+  // image tail) for fwd/dgrad, PARADIS_AMAX_PARTIALS words for wgrad; b_amax: PARADIS_AMAX_PARTIALS words.
+  const uint32_t* a_amax; const uint32_t* b_amax;
+  // PARADIS_GEMM_BF16 only (round 6): which tensors are STORED as bf16 (2 bytes per element; strides stay in elements).
+  // IO_B16: the activation operand B (fwd: X, dgrad: dY) - pw_gemm_b16_kernel stages it by LDS-DMA and reads it with
+  // ds_read_b64_tr_b16; IO_C16: the output C (and zout); IO_ZM16: zmul.  Residual, bias and maps are always fp32.
+  int io16;
+  // (PARADIS_GEMM_BF16, the reference's bf16-mixed mode: the result is rounded to bf16 where the reference's autocast
+  //  conv2d rounds it - the pre-activation and the activated value (fwd), the activation-gradient product (dgrad) -
+  //  before the fp32 residual / blend; a compile-time property of pw_gemm_bf16_k32_kernel's epilogue.  Stored as fp32.)
+};
+
+// launchers of the bf16-mixed kernels (gemm_amp_fwd.hip, gemm_amp_wgrad.hip; called from gemm.hip)
+int pd_amp_launch_fwd(const GemmArgs& d, hipStream_t st);
+// kind: 0 = 128 x 128 tile, fp32 operands; 1 = 128 x 128 with a bf16 operand; 2 = 256 x 128; 3 = 256 x 256 (grid: the caller's)
+int pd_amp_launch_wgrad(const GemmArgs& g, int io16, int kind, int grid, hipStream_t st);
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int BM = 128, BN = 128;
+
+// ---- low-rank bias (GlobalBias with projection) accumulated straight into the MFMA accumulators:
+//   acc[m,n] += sum_c pwT[c,m] * m8[c,n].  pwT is the transposed projection weight so that the four
+//   consecutive rows (r&3) of an accumulator group come from one 16-byte load (needs M % 4 == 0).
+//   One channel at a time keeps the live set at acc + 8 registers.
+__device__ __forceinline__ void gemm_add_projection(const GemmArgs& g, f32x16 (&acc)[2][2], int m0, int n0,
+                                                    int wm, int wn, int li, int lh) {
+  const int nc0 = min(n0 + wn * 64 + li, g.N - 1), nc1 = min(n0 + wn * 64 + 32 + li, g.N - 1);
+#pragma unroll 1
+  for (int c = 0; c < g.cin; ++c) {
+    const float mb0 = g.m8[(int64_t)c * g.N + nc0], mb1 = g.m8[(int64_t)c * g.N + nc1];
+    const float* pc = g.pw + (int64_t)c * g.M;
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) {
+      const int mrow = m0 + wm * 64 + tm * 32 + 4 * lh;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int mr = mrow + 8 * j;
+        const float4 p4 = (mr < g.M) ? *reinterpret_cast<const float4*>(pc + mr) : make_float4(0.f, 0.f, 0.f, 0.f);
+        acc[tm][0][4 * j + 0] += p4.x * mb0; acc[tm][1][4 * j + 0] += p4.x * mb1;
+        acc[tm][0][4 * j + 1] += p4.y * mb0; acc[tm][1][4 * j + 1] += p4.y * mb1;
+        acc[tm][0][4 * j + 2] += p4.z * mb0; acc[tm][1][4 * j + 2] += p4.z * mb1;
+        acc[tm][0][4 * j + 3] += p4.w * mb0; acc[tm][1][4 * j + 3] += p4.w * mb1;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ float gate_sigmoid(float a) { return 1.0f / (1.0f + expf(-a)); }
+// value of x rounded to bf16 (round to nearest even; a NaN stays a NaN: v_cvt_pk_bf16_f32)
+__device__ __forceinline__ float round_bf16(float x) { return (float)(__bf16)x; }
+// Activations of the bf16-mixed epilogue (R16): the value is rounded to bf16 - 8 significant bits - in the next instruction, so
+// the hardware's 1-ulp exp2 / reciprocal stand in for expf and the IEEE division of act_apply / act_grad (common.h): about 9
+// instead of about 29 vector instructions per element in an epilogue that was bound by exactly those (sixteen waves x 64 elements
+// per lane and tensor).  SiLU only; GELU keeps the library functions.  The fp32-width schemes never call these.
+__device__ __forceinline__ float sigmoid_r16(float z) {
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * z));
+}
+__device__ __forceinline__ float act_apply_r16(float z, int act) {
+  return act == PARADIS_ACT_SILU ? z * sigmoid_r16(z) : act_apply(z, act);
+}
+__device__ __forceinline__ float act_grad_r16(float z, int act) {
+  if (act == PARADIS_ACT_SILU) {
+    const float s = sigmoid_r16(z);
+    return s * (1.0f + z * (1.0f - s));
+  }
+  return act_grad(z, act);
+}
+// (An epilogue / k-loop stagger - the second workgroup of every CU of the first round starting late by 64-256 x 512 cycles,
+//  so that one workgroup's store-bound epilogue runs under the other's MFMA-bound k-loop - was measured on the bf16-mixed
+//  and the bf16x3 kernels and lost 0-10 % at every setting: profiles/r06_stagger_sweep.txt.  Not kept.)
+[[maybe_unused]] constexpr int IO_B16 = 1, IO_C16 = 2, IO_ZM16 = 4, IO_A16 = 8;     // GemmArgs::io16 (IO_A16: wgrad's dY operand)
+// bf16 storage: element i of a bf16 array as a float / a bf16-VALUED float (already rounded) into a bf16 array
+__device__ __forceinline__ float ld_bf16(const void* p, int64_t i) {
+  return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(p)[i] << 16);
+}
+__device__ __forceinline__ void st_bf16(void* p, int64_t i, float v) {
+  reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)(__float_as_uint(v) >> 16);
+}
+
+// ---- epilogue: C/D layout of v_mfma_f32_32x32x2_f32: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+//   v = acc (+bias[m]) (+map[m,n]); zout = v; v = zmul ? v*act'(zmul) : act(v);
+//   v = gate ? res + sigmoid(gate[m]) (v - res) : v + res; C = v
+// Interior tiles take a path without per-element guards in which all loads of one 32-row group are
+// issued back to back (the guarded form serialises every load behind an s_waitcnt vmcnt(0)).
+// R16 (compile time: only the bf16-mixed kernel instantiates it, the fp32 schemes' epilogue is the round-4 code): round
+// the pre-activation and the activated / activation-gradient value to bf16 (see the note in GemmArgs)
+template <bool R16 = false, bool C16 = false, bool ZM16 = false>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2][2], int bz, int m0,
+                                              int n0, int wm, int wn, int li, int lh) {
+  float* Cb = g.C + (int64_t)bz * g.c_bs;
+  const float* resb = g.res ? g.res + (int64_t)bz * g.res_bs : nullptr;
+  const float* zmulb = g.zmul ? g.zmul + (int64_t)bz * g.zmul_bs : nullptr;
+  float* zoutb = g.zout ? g.zout + (int64_t)bz * g.zout_bs : nullptr;
+  // bf16-stored tensors (compile-time properties of the bf16-mixed kernels' instantiations - as run-time branches they
+  // cost the 128-register kernels 256 bytes of scratch and 100 us per launch): the same element offsets on 2-byte elements
+  static_assert(R16 || !(C16 || ZM16), "bf16-stored tensors exist in the bf16-mixed scheme only");
+  (void)sizeof(char[C16 + ZM16 + 1]);
+  const int64_t cb16 = (int64_t)bz * g.c_bs, zmb16 = (int64_t)bz * g.zmul_bs, zob16 = (int64_t)bz * g.zout_bs;
+  if (g.pw) gemm_add_projection(g, acc, m0, n0, wm, wn, li, lh);
+  if constexpr (C16 || ZM16) {
+    // bf16-stored tensors of an interior tile move as PACKED PAIRS: a lane holds pixel li of the wave's two 32-column MFMA
+    // tiles (columns li and 32 + li of one row) - as 2-byte accesses a row of a tile is a 64-byte segment per instruction.
+    // Adjacent lanes swap one value each (even lane: its tile-1 value for the odd lane's tile-0 value), after which the even
+    // lane holds columns (li, li + 1) of tile 0 and the odd lane columns (31 + li, 32 + li): one dword per lane, 128 contiguous
+    // bytes per row and instruction, half the instructions.  Loads of a bf16 zmul run the same exchange backwards.
+    if (m0 + BM <= g.M && n0 + BN <= g.N && ((g.ldc | g.c_bs | g.zout_bs | g.zmul_bs) & 1) == 0) {
+      const bool odd = (li & 1) != 0;
+      const uint32_t sel = odd ? 0x07060302u : 0x03020706u;       // v_perm_b32(keep, recv): {lo, hi} halves of the dword
+      const int pcol = odd ? 31 + li : li;                         // first column of this lane's pair (even)
+      auto swap1 = [](float v) __attribute__((always_inline)) {   // the neighbour's value (lanes 2u <-> 2u + 1)
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false));
+      };
+      auto pack = [&](float a0, float a1) __attribute__((always_inline)) {      // a0 / a1: this lane's tile-0 / tile-1 value (bf16-valued)
+        const float keep = odd ? a1 : a0, recv = swap1(odd ? a0 : a1);
+        return __builtin_amdgcn_perm(__float_as_uint(keep), __float_as_uint(recv), sel);
+      };
+      auto unpack = [&](uint32_t w, float& t0, float& t1) __attribute__((always_inline)) {
+        const float wlo = __uint_as_float(w << 16), whi = __uint_as_float(w & 0xffff0000u);
+        const float recv = swap1(odd ? wlo : whi);
+        t0 = odd ? recv : wlo;
+        t1 = odd ? whi : recv;
+      };
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm) {
+        const int mrow = m0 + wm * 64 + tm * 32 + 4 * lh;
+        const int64_t base = (int64_t)mrow * g.ldc + n0 + wn * 64 + li;          // tile 0; tile 1: + 32
+        const int64_t pbase = (int64_t)mrow * g.ldc + n0 + wn * 64 + pcol;       // this lane's pair
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {   // 4 accumulator registers of each tile at a time
+          float v[2][4], t[2][4];
+          // register r = 4h + q  ->  row offset q + 8h
+#define ROWOFF(q) ((int64_t)((q) + 8 * h) * g.ldc)
+#pragma unroll
+          for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[tn][q] = acc[tm][tn][4 * h + q];
+          if (g.bias) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) t[0][q] = g.bias[mrow + q + 8 * h];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { v[0][q] += t[0][q]; v[1][q] += t[0][q]; }
+          }
+          if (g.map) {
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) t[tn][q] = g.map[base + 32 * tn + ROWOFF(q)];
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[tn][q] += t[tn][q];
+          }
+#pragma unroll
+          for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[tn][q] = round_bf16(v[tn][q]);
+          if (zoutb) {
+            if constexpr (C16) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q)
+                reinterpret_cast<uint32_t*>(g.zout)[(zob16 + pbase + ROWOFF(q)) >> 1] = pack(v[0][q], v[1][q]);
+            } else {
+#pragma unroll
+              for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) zoutb[base + 32 * tn + ROWOFF(q)] = v[tn][q];
+            }
+          }
+          if (zmulb) {
+            if constexpr (ZM16) {
+              uint32_t w[4];
+#pragma unroll
+              for (int q = 0; q < 4; ++q) w[q] = reinterpret_cast<const uint32_t*>(g.zmul)[(zmb16 + pbase + ROWOFF(q)) >> 1];
+#pragma unroll
+              for (int q = 0; q < 4; ++q) unpack(w[q], t[0][q], t[1][q]);
+            } else {
+#pragma unroll
+              for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) t[tn][q] = zmulb[base + 32 * tn + ROWOFF(q)];
+            }
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[tn][q] *= act_grad_r16(t[tn][q], g.act);
+          } else if (g.act) {
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[tn][q] = act_apply_r16(v[tn][q], g.act);
+          }
+          if (zmulb || g.act) {
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) v[tn][q] = round_bf16(v[tn][q]);
+          }
+          if (resb) {
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) t[tn][q] = resb[base + 32 * tn + ROWOFF(q)];
+            if (g.gate) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+                const float gm = gate_sigmoid(g.gate[mrow + q + 8 * h]);
+                v[0][q] = fmaf(gm, v[0][q] - t[0][q], t[0][q]);
+                v[1][q] = fmaf(gm, v[1][q] - t[1][q], t[1][q]);
+              }
+            } else {
+#pragma unroll
+              for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[tn][q] += t[tn][q];
+            }
+          }
+          if constexpr (C16) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              reinterpret_cast<uint32_t*>(g.C)[(cb16 + pbase + ROWOFF(q)) >> 1] = pack(v[0][q], v[1][q]);
+          } else {
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) Cb[base + 32 * tn + ROWOFF(q)] = v[tn][q];
+          }
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+#undef ROWOFF
+        }
+      }
+      return;
+    }
+  }
+  if (m0 + BM <= g.M && n0 + BN <= g.N) {
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) {
+      const int mrow = m0 + wm * 64 + tm * 32 + 4 * lh;
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) {
+        const int64_t base = (int64_t)mrow * g.ldc + n0 + wn * 64 + tn * 32 + li;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {   // 8 accumulator registers at a time keeps the kernel <= 128 VGPRs
+          float v[8], t[8];
+          // register r = 8h + q  ->  row offset (q&3) + 8*(2h + (q>>2))
+#define ROWOFF(q) ((int64_t)(((q) & 3) + 8 * (2 * h + ((q) >> 2))) * g.ldc)
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v[q] = acc[tm][tn][8 * h + q];
+          if (g.bias) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) t[q] = g.bias[mrow + (q & 3) + 8 * (2 * h + (q >> 2))];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] += t[q];
+          }
+          if (g.map) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) t[q] = g.map[base + ROWOFF(q)];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] += t[q];
+          }
+          if constexpr (R16) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = round_bf16(v[q]);
+          }
+          if (zoutb) {
+            if constexpr (C16) {
+#pragma unroll
+              for (int q = 0; q < 8; ++q) st_bf16(g.zout, zob16 + base + ROWOFF(q), v[q]);
+            } else {
+#pragma unroll
+              for (int q = 0; q < 8; ++q) zoutb[base + ROWOFF(q)] = v[q];
+            }
+          }
+          if (zmulb) {
+            if constexpr (ZM16) {
+#pragma unroll
+              for (int q = 0; q < 8; ++q) t[q] = ld_bf16(g.zmul, zmb16 + base + ROWOFF(q));
+            } else {
+#pragma unroll
+              for (int q = 0; q < 8; ++q) t[q] = zmulb[base + ROWOFF(q)];
+            }
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] *= R16 ? act_grad_r16(t[q], g.act) : act_grad(t[q], g.act);
+          } else if (g.act) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = R16 ? act_apply_r16(v[q], g.act) : act_apply(v[q], g.act);
+          }
+          if constexpr (R16) {
+            if (zmulb || g.act) {
+#pragma unroll
+              for (int q = 0; q < 8; ++q) v[q] = round_bf16(v[q]);
+            }
+          }
+          if (resb) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) t[q] = resb[base + ROWOFF(q)];
+            if (g.gate) {   // h + sigmoid(alpha) (adv - h): the arithmetic of gated_blend_fwd_kernel (misc.hip), bit for bit
+#pragma unroll
+              for (int q = 0; q < 8; ++q) {
+                const float gm = gate_sigmoid(g.gate[mrow + (q & 3) + 8 * (2 * h + (q >> 2))]);
+                v[q] = fmaf(gm, v[q] - t[q], t[q]);
+              }
+            } else {
+#pragma unroll
+              for (int q = 0; q < 8; ++q) v[q] += t[q];
+            }
+          }
+          if constexpr (C16) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) st_bf16(g.C, cb16 + base + ROWOFF(q), v[q]);
+          } else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) Cb[base + ROWOFF(q)] = v[q];
+          }
+          // keep the scheduler from hoisting the next chunk's loads (register pressure)
+          asm volatile("" ::: "memory");
+          __builtin_amdgcn_sched_barrier(0);
+#undef ROWOFF
+        }
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      if (m >= g.M) continue;
+      const float bv = g.bias ? g.bias[m] : 0.f;
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn) {
+        const int n = n0 + wn * 64 + tn * 32 + li;
+        if (n >= g.N) continue;
+        const int64_t off = (int64_t)m * g.ldc + n;
+        float v = acc[tm][tn][r] + bv;
+        if (g.map) v += g.map[off];
+        if constexpr (R16) v = round_bf16(v);
+        if (zoutb) { if constexpr (C16) st_bf16(g.zout, zob16 + off, v); else zoutb[off] = v; }
+        if (zmulb) {
+          const float zm = ZM16 ? ld_bf16(g.zmul, zmb16 + off) : zmulb[off];
+          v *= R16 ? act_grad_r16(zm, g.act) : act_grad(zm, g.act);
+        } else if (g.act) {
+          v = R16 ? act_apply_r16(v, g.act) : act_apply(v, g.act);
+        }
+        if constexpr (R16) { if (zmulb || g.act) v = round_bf16(v); }
+        if (resb) {
+          const float r = resb[off];
+          v = g.gate ? fmaf(gate_sigmoid(g.gate[m]), v - r, r) : v + r;
+        }
+        if constexpr (C16) st_bf16(g.C, cb16 + off, v); else Cb[off] = v;
+      }
+    }
+  }
+}
+
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+
+// ======================================================================================
+// Split-bf16 kernels: the same fp32 GEMMs on the bf16 matrix pipe (16x the f32 MFMA rate).
+// Every fp32 operand value x is written as h + m + l with h = bf16(x), m = bf16(x - h),
+// l = bf16(x - h - m): three bf16 numbers carry 3 x 8 = 24 significand bits, so the split is exact.
+// a*b is accumulated in fp32 from the six partial products of weight >= 2^-16,
+//     ah*bh + ah*bm + am*bh + ah*bl + al*bh + am*bm        (dropped: am*bl, al*bm, al*bl <= 2^-23 |ab|)
+// v_mfma_f32_32x32x16_bf16 forms the 8x8-bit products exactly and accumulates in fp32, 6/16 roundings
+// per k instead of the f32 MFMA's 1: the measured error against fp64 is below the f32 kernels'
+// (tests/test_hip_gemm_split.py).  Non-finite inputs come out as NaN (Inf - Inf in the split).
+//
+// LDS image of a 128 x 16 operand tile: [split 3][k-half 2][row 128] chunks of 16 B = 8 bf16
+// (k = 8*half + 0..7), so that one ds_read_b128 per lane (row = lane&31, half = lane>>5) is the
+// MFMA operand.  Weights are split once per call into that image in global memory
+// (split_weights_kernel) and move by LDS-DMA; activations are split in registers while staged.
+// 2 stages x 24 KiB => 3 workgroups per CU.
+// ======================================================================================
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// LDS images are accessed through a clang vector type, not HIP's u32x4 struct: behind a struct-typed
+// ds_read the compiler inserts an s_waitcnt vmcnt for every LDS-DMA still in flight (alias rule),
+// which would serialise the DMA rings; vector-typed reads do not get that wait.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int SBK = 16;                  // k depth of a tile = one bf16 / f16 MFMA
+constexpr int SCH = 128;                 // chunks per k-half row of an unpadded image
+constexpr int SCHP = 128 + 8;            // padded variant (wgrad: lane pairs write both k-halves of a row)
+// NP = number of planes of an operand image = terms of the split: 3 = bf16 h/m/l (exact, six products),
+// 2 = f16 h/l of the scaled value (22 significand bits, three products), 1 = the value rounded to bf16 (ONE product:
+// PARADIS_GEMM_BF16, the arithmetic of the reference's bf16-mixed training mode - train.py:56 - never the fp32 path's)
+constexpr int simg(int np) { return np * 2 * SCH; }      // chunks per operand per stage (12 / 8 KiB)
+constexpr int simgp(int np) { return np * 2 * SCHP; }
+
+// ---- sign checkerboard (round 4) ---------------------------------------------------------------------------------
+// What the bf16 / f16 MFMA does with its accumulator input (tools/mfma_round_probe.hip, gfx950): the sixteen products
+// are summed first; the smaller of {C, product sum} is then aligned to the larger one's exponent, and when the smaller
+// one is C its low bits are dropped by a two's-complement FLOOR (C = -2^-26 against a product sum of 1 - 1 comes out as
+// -2^-24).  Whenever a k-tile's product sum outweighs the running accumulator - the first tiles, and every later zero
+// crossing: ~5 times per K = 1024 dot product of zero-mean data - the result moves half a granule towards -infinity.
+// The f32 MFMA (an fma chain, round to nearest) has no such term.  Measured (tools/gemm_bias_check.py, N(0,1) data,
+// unit u = 2^-24 rms(C)): every output of the six-product GEMM carried the SAME offset, -0.9 u on top of 8.2 u of
+// zero-mean noise (f32 MFMA: +0.002 u on 9.6 u), -8 u on the weight gradient's 32,768-term sums.  Harmless per element,
+// but sums over pixels or channels of a GEMM output (bias / ChannelNorm parameter gradients over 32,768 points, the
+// per-pixel channel statistics) add the offset coherently where noise averages out: 0.9 u x 32,768 against 8.2 u x 181.
+// Remedy without a second accumulator set or VALU work per tile: run alternate 32-row x 64-column blocks of the output
+// in the NEGATED space.  The weight image holds the rows of odd 32-row blocks with the opposite sign (free: written once
+// by split_weights_kernel), the activation columns of odd 64-column blocks - the columns ONE wave stages - are negated
+// while they are split in registers (-x splits exactly into -h, -m, -l; in the 128 x 256 kernel the sign is a
+// compile-time property of the code path a staging wave takes, so it rides on source modifiers), so block (tm) of
+// compute wave (wm, wn) accumulates (-1)^(tm+wn) C: there the floor acts on -C, the offset of C is +0.9 u, and the
+// epilogue flips those blocks back.  The offset is still there per element; it alternates in sign every 32 rows and
+// 64 columns and cancels in every sum over more than a block.  The weight gradient alternates by K-range slab instead (odd slabs negate dY): there the offsets of an
+// element's slabs cancel in the slab sum.
+#ifndef SPLIT_SIGNED          // (-DSPLIT_SIGNED=0: the unsigned accumulation of rounds 1-3, for A/B runs)
+#define SPLIT_SIGNED 1
+#endif
+#ifndef SPLIT_SIGNED_WGRAD    // (the slab alternation of the weight gradient alone)
+#define SPLIT_SIGNED_WGRAD SPLIT_SIGNED
+#endif
+// sign bit of the staging thread's activation column (column = tid & 127 of a 128-column tile)
+__device__ __forceinline__ uint32_t split_flip_mask(int col) { return SPLIT_SIGNED && (col & 64) ? 0x80000000u : 0u; }
+__device__ __forceinline__ void flip8(float (&y)[8], const float (&x)[8], uint32_t mask) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) y[j] = __uint_as_float(__float_as_uint(x[j]) ^ mask);
+}
+// the row blocks tm with (tm + wn) odd hold -C (wn = the wave's 64-column half: the sign of its activation columns)
+__device__ __forceinline__ void split_unflip(f32x16 (&acc)[2][2], int wn) {
+  if (!SPLIT_SIGNED) return;
+  const float s0 = wn ? -1.f : 1.f, s1 = -s0;          // wave-uniform
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[0][tn][r] *= s0; acc[1][tn][r] *= s1; }
+}
+
+// ---- f16x2 scheme ------------------------------------------------------------------------------
+// x' = x 2^e with e chosen per TENSOR so that max |x'| lies in [2^14, 2^15) (fp16 holds 65504);
+// h = f16(x'), l = f16(x' - h): x' = h + l up to 2^-23 |x'|, and - fp16 being a fixed-point format below
+// 2^-14 - up to 2^-25 absolutely, i.e. 2^-39 of the tensor's largest magnitude.  a b is accumulated in
+// fp32 from  al bh + ah bl + ah bh  (dropped: al bl <= 2^-22 |ab|); the f16 MFMA forms the 11x11-bit
+// products exactly.  The result is unscaled by 2^-(ea+eb) in the epilogue (two exact multiplications).
+// Error against fp64 of a K = 1024 product of N(0,1) operands: 5.1e-7 of max |C| (SGEMM: 5.8e-7); what
+// it gives up against the bf16x3 scheme is elements more than ~2^17 below their tensor's maximum, which
+// keep an ABSOLUTE accuracy of 2^-39 max|x| instead of a relative one.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// scale 2^e and its inverse from the bits of max |x| (biased exponent E: e = 14 - (E - 127)); a zero or
+// tiny maximum takes the largest scale.  A non-finite maximum (an Inf or NaN somewhere in the tensor) has no
+// meaningful scale: the scale becomes NaN and with it the whole product - loudly wrong, never silently rescaled.
+__device__ __forceinline__ void scale_from_amax(uint32_t amax_bits, float& s, float& inv) {
+  int E = (int)((amax_bits >> 23) & 0xffu);
+  const bool finite = E != 255;
+  E = E < 15 ? 15 : E;
+  s = finite ? __uint_as_float((uint32_t)(268 - E) << 23) : __uint_as_float(0x7fc00000u);
+  inv = __uint_as_float((uint32_t)(E - 14) << 23);
+}
+
+// max of PARADIS_AMAX_PARTIALS (= 1024) words, by a 256-thread workgroup; every thread gets the result
+__device__ __forceinline__ uint32_t reduce_amax_partials(const uint32_t* __restrict__ p) {
+  __shared__ uint32_t red[4];
+  const int tid = threadIdx.x;
+  uint32_t m = max(max(p[tid], p[tid + 256]), max(p[tid + 512], p[tid + 768]));
+  m = wave_umax_lane63(m);
+  if ((tid & 63) == 63) red[tid >> 6] = m;
+  __syncthreads();
+  m = max(max(red[0], red[1]), max(red[2], red[3]));
+  __syncthreads();
+  return m;
+}
+
+// (x0, x1) 2^e -> packed halves h, l.  v_fma_mix*: fp32 FMA, result rounded once to f16; x s and
+// x s - h are exact in fp32, so h and l are the correctly rounded values.
+__device__ __forceinline__ void split2_pair(float x0, float x1, float s, uint32_t& h, uint32_t& l) {
+  uint32_t hh, ll;
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hh) : "v"(x0), "v"(s));
+  asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hh) : "v"(x1), "v"(s));
+  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(ll) : "v"(x0), "v"(s), "v"(hh));
+  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(ll) : "v"(x1), "v"(s), "v"(hh));
+  h = hh; l = ll;
+}
+
+__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
+  const f32x2 v = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));   // v_cvt_pk_bf16_f32, a in the low half
+}
+
+__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) {
+  h = pack_bf16(x0, x1);
+  const float r0 = x0 - __uint_as_float(h << 16), r1 = x1 - __uint_as_float(h & 0xffff0000u);
+  m = pack_bf16(r0, r1);
+  l = pack_bf16(r0 - __uint_as_float(m << 16), r1 - __uint_as_float(m & 0xffff0000u));
+}
+
+__device__ __forceinline__ void split8(const float (&x)[8], u32x4& h, u32x4& m, u32x4& l) {
+  uint32_t hh[4], mm[4], ll[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) split_pair(x[2 * i], x[2 * i + 1], hh[i], mm[i], ll[i]);
+  h = (u32x4){hh[0], hh[1], hh[2], hh[3]};
+  m = (u32x4){mm[0], mm[1], mm[2], mm[3]};
+  l = (u32x4){ll[0], ll[1], ll[2], ll[3]};
+}
+
+// eight values rounded to bf16 (the one plane of PARADIS_GEMM_BF16)
+__device__ __forceinline__ u32x4 round8(const float (&x)[8]) {
+  return (u32x4){pack_bf16(x[0], x[1]), pack_bf16(x[2], x[3]), pack_bf16(x[4], x[5]), pack_bf16(x[6], x[7])};
+}
+
+__device__ __forceinline__ void split8_f16(const float (&x)[8], float s, u32x4& h, u32x4& l) {
+  uint32_t hh[4], ll[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) split2_pair(x[2 * i], x[2 * i + 1], s, hh[i], ll[i]);
+  h = (u32x4){hh[0], hh[1], hh[2], hh[3]};
+  l = (u32x4){ll[0], ll[1], ll[2], ll[3]};
+}
+
+#define SPLIT_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), C, 0, 0, 0)
+// The six partial products of one 32x32 block, smallest first.  (An order in which consecutive MFMAs
+// share an operand register, snaking over the four blocks of a wave tile, measured +0.5 % - nothing -
+// once the A/B alternated the variants: a fixed order of variants shows 3-5 % in favour of whichever
+// runs later.)
+#define SPLIT_BLOCK(AH, AM, AL, BH, BM_, BL, C) \
+  SPLIT_MFMA(AM, BM_, C); SPLIT_MFMA(AL, BH, C); SPLIT_MFMA(AH, BL, C); \
+  SPLIT_MFMA(AM, BH, C);  SPLIT_MFMA(AH, BM_, C); SPLIT_MFMA(AH, BH, C)
+#define SPLIT_MFMA16(A, B, C) C = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A), __builtin_bit_cast(f16x8, B), C, 0, 0, 0)
+
+// one k-tile: fragments of both operands from the images at As/Bs (chunk pointers at this lane's
+// row of block 0, k-half lh), plane stride PA/PB chunks ...
+template <int NP> struct SplitFrags { u32x4 a[NP][2], b[NP][2]; };
+template <int NP, int PA, int PB>
+__device__ __forceinline__ void split_tile_read(const u32x4* As, const u32x4* Bs, SplitFrags<NP>& f) {
+  // in the order of first use by split_tile_mfma (block (0,0): m.m, l.h, h.l first; l.h, h.l for two
+  // planes), so that the counted lgkmcnt waits let the first MFMAs start after two reads
+  if constexpr (NP == 3) {
+    f.a[1][0] = As[PA];          f.b[1][0] = Bs[PB];
+    f.a[2][0] = As[2 * PA];      f.b[0][0] = Bs[0];
+    f.a[0][0] = As[0];           f.b[2][0] = Bs[2 * PB];
+    f.b[1][1] = Bs[PB + 32];     f.b[0][1] = Bs[32];          f.b[2][1] = Bs[2 * PB + 32];
+    f.a[1][1] = As[PA + 32];     f.a[2][1] = As[2 * PA + 32]; f.a[0][1] = As[32];
+  } else if constexpr (NP == 2) {
+    f.a[1][0] = As[PA];          f.b[0][0] = Bs[0];
+    f.a[0][0] = As[0];           f.b[1][0] = Bs[PB];
+    f.b[0][1] = Bs[32];          f.b[1][1] = Bs[PB + 32];
+    f.a[1][1] = As[PA + 32];     f.a[0][1] = As[32];
+  } else {
+    f.a[0][0] = As[0];  f.b[0][0] = Bs[0];
+    f.b[0][1] = Bs[32]; f.a[0][1] = As[32];
+  }
+}
+// ... then the 24 (12) MFMAs, smallest products first
+template <int NP>
+__device__ __forceinline__ void split_tile_mfma(const SplitFrags<NP>& f, f32x16 (&acc)[2][2]) {
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn) {
+      if constexpr (NP == 3) {
+        SPLIT_BLOCK(f.a[0][tm], f.a[1][tm], f.a[2][tm], f.b[0][tn], f.b[1][tn], f.b[2][tn], acc[tm][tn]);
+      } else if constexpr (NP == 2) {
+        SPLIT_MFMA16(f.a[1][tm], f.b[0][tn], acc[tm][tn]);
+        SPLIT_MFMA16(f.a[0][tm], f.b[1][tn], acc[tm][tn]);
+        SPLIT_MFMA16(f.a[0][tm], f.b[0][tn], acc[tm][tn]);
+      } else {
+        SPLIT_MFMA(f.a[0][tm], f.b[0][tn], acc[tm][tn]);
+      }
+    }
+}
+
+// f16x2: C = 2^-(ea+eb) acc, two exact multiplications (their product may lie outside the fp32 range)
+__device__ __forceinline__ void split_unscale(f32x16 (&acc)[2][2], float inv_a, float inv_b) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] * inv_a) * inv_b;
+}
+
+// ---- the weight-gradient kernel of the split schemes: gemm.hip launches NP = 3 and 2, gemm_amp_wgrad.hip NP = 1 ---------
+// wgrad: dW[M,N'] = sum over (sample, p) A[m][p] B[n][p], both operands p-contiguous fp32, both split
+// in registers.  Thread t stages 8 consecutive p of row t>>1 (k-half t&1) of each operand.
+// Needs K % 16 == 0 and 16-B aligned rows (host-checked; otherwise the f32 kernels run).
+// Same pipeline as the fwd/dgrad kernel: loads two tiles ahead into alternating register sets (inline asm,
+// counted waits), the two splits of tile t+1 between the MFMAs of tile t, raw barriers, one MFMA block
+// per tile.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// (A soft rendezvous of a K-range slab's tiles - round 5: FETCH_SIZE 8.48 -> 4.06 GB per launch at 128 x 256, kernel 13 %
+//  slower - was measured and removed: DESIGN_HISTORY.md section 4.1d, profiles/r05_wgrad_rendezvous.txt.)
+template <int NP>
+__global__ void __launch_bounds__(256, 3)
+pw_gemm_wgrad_split_kernel(GemmArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int SIMGP = simgp(NP);
+  u32x4* img = reinterpret_cast<u32x4*>(lds);        // [2 stages][A|B][SIMGP]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int li = lane & 31, lh = lane >> 5;
+
+  const int MT = (g.M + BM - 1) / BM, NT = (g.N + BN - 1) / BN;
+  int L;
+  {
+    const int nwg = gridDim.x, id = blockIdx.x;
+    const int q = nwg >> 3, r = nwg & 7, xcd = id & 7;
+    L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
+  }
+  const int mt = L % MT, nt = (L / MT) % NT, bz = L / (MT * NT);
+  const int m0 = mt * BM, n0 = nt * BN;
+  const int KT = g.K / SBK;
+  const int64_t total = (int64_t)g.inner * KT;
+  const int t_begin = (int)(total * bz / g.nbatch);
+  const int T = (int)(total * (bz + 1) / g.nbatch) - t_begin;
+
+  const int srow = tid >> 1, sh = tid & 1;
+  const float* Ag = g.A + (int64_t)min(m0 + srow, g.M - 1) * g.lda + sh * 8;
+  const float* Bg = g.B + (int64_t)min(n0 + srow, g.N - 1) * g.ldb + sh * 8;
+
+  // (sample, k-tile) of the next tile to fetch, advanced incrementally
+  int f_ib = t_begin / KT, f_kt = t_begin - f_ib * KT;
+  struct Regs { f32x4 a0, a1, b0, b1; };
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  Regs r0{zero4, zero4, zero4, zero4}, r1 = r0;   // defined values: the surplus split of a one-tile range reads r1
+  auto fetch = [&](Regs& r) __attribute__((always_inline)) {
+    const float* a = Ag + (int64_t)f_ib * g.a_is + (int64_t)f_kt * SBK;
+    const float* b = Bg + (int64_t)f_ib * g.b_is + (int64_t)f_kt * SBK;
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r.a0) : "v"(a) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=&v"(r.a1) : "v"(a) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r.b0) : "v"(b) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=&v"(r.b1) : "v"(b) : "memory");
+    if (++f_kt == KT) { f_kt = 0; ++f_ib; }
+  };
+  // at most N younger vector-memory operations outstanding; registers as asm inputs (see USE_X)
+#define USE_R(r, N) do { asm volatile("s_waitcnt vmcnt(" #N ")" :: "v"(r.a0), "v"(r.a1), "v"(r.b0), "v"(r.b1) : "memory"); \
+                         __builtin_amdgcn_sched_barrier(0); } while (0)
+  const bool do_rowsum = g.rowsum != nullptr && nt == 0;
+  float rs = 0.f;
+  float sc_a = 1.f, sc_b = 1.f, inv_a = 1.f, inv_b = 1.f;
+  if constexpr (NP == 2) {
+    scale_from_amax(reduce_amax_partials(g.a_amax), sc_a, inv_a);
+    scale_from_amax(reduce_amax_partials(g.b_amax), sc_b, inv_b);
+  }
+  // the offset of the MFMA's accumulator alignment (see "sign checkerboard") cancels between an element's slabs
+  const uint32_t slab_flip = (SPLIT_SIGNED_WGRAD && (bz & 1)) ? 0x80000000u : 0u;      // workgroup-uniform
+  if constexpr (NP == 2) sc_a = __uint_as_float(__float_as_uint(sc_a) ^ slab_flip);
+  auto split_store = [&](const Regs& r, int st, bool keep) __attribute__((always_inline)) {
+    const float xa[8] = {r.a0.x, r.a0.y, r.a0.z, r.a0.w, r.a1.x, r.a1.y, r.a1.z, r.a1.w};
+    const float xb[8] = {r.b0.x, r.b0.y, r.b0.z, r.b0.w, r.b1.x, r.b1.y, r.b1.z, r.b1.w};
+    // bias gradient: row sums of the staged dY values (a select, not a product: the surplus split of the
+    // last tile works on stale registers that may hold NaNs)
+    const float add = ((xa[0] + xa[1]) + (xa[2] + xa[3])) + ((xa[4] + xa[5]) + (xa[6] + xa[7]));
+    rs += keep ? add : 0.f;
+    u32x4* o = img + st * 2 * SIMGP + sh * SCHP + srow;
+    if constexpr (NP == 3) {
+      u32x4 ha, ma, la, hb, mb, lb;
+      float xs[8];
+      flip8(xs, xa, slab_flip);    // sign alternation by slab: odd K-ranges accumulate -dW
+      split8(xs, ha, ma, la);
+      split8(xb, hb, mb, lb);
+      o[0] = ha; o[2 * SCHP] = ma; o[4 * SCHP] = la;
+      o += SIMGP;
+      o[0] = hb; o[2 * SCHP] = mb; o[4 * SCHP] = lb;
+    } else if constexpr (NP == 1) {
+      float xs[8];
+      flip8(xs, xa, slab_flip);
+      o[0] = round8(xs);
+      o[SIMGP] = round8(xb);
+    } else {
+      u32x4 ha, la, hb, lb;
+      split8_f16(xa, sc_a, ha, la);
+      split8_f16(xb, sc_b, hb, lb);
+      o[0] = ha; o[2 * SCHP] = la;
+      o += SIMGP;
+      o[0] = hb; o[2 * SCHP] = lb;
+    }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  if (T > 0) {
+    fetch(r0);
+    if (T > 1) { fetch(r1); USE_R(r0, 4); } else { USE_R(r0, 0); }
+    split_store(r0, 0, do_rowsum);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+  auto step = [&](int t, int cur, Regs& rload, Regs& rsplit) __attribute__((always_inline)) {
+    const u32x4* As = img + cur * 2 * SIMGP + lh * SCHP + wm * 64 + li;
+    const u32x4* Bs = img + (cur * 2 + 1) * SIMGP + lh * SCHP + wn * 64 + li;
+    SplitFrags<NP> f;
+    split_tile_read<NP, 2 * SCHP, 2 * SCHP>(As, Bs, f);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t + 2 < T) { fetch(rload); USE_R(rsplit, 4); }
+    else USE_R(rsplit, 0);
+    // one basic block for every tile; the last tile's split is surplus (stage nobody reads, keep = 0)
+    split_tile_mfma<NP>(f, acc);
+    split_store(rsplit, cur ^ 1, do_rowsum && t + 1 < T);
+    if constexpr (NP > 1) {
+#pragma unroll
+    for (int i = 0; i < (NP == 3 ? 24 : 12); ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+      __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);   // five VALU of the two splits
+    }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  };
+  for (int t = 0; t < T; t += 2) {
+    step(t, 0, r0, r1);
+    if (t + 1 < T) step(t + 1, 1, r1, r0);
+  }
+#undef USE_R
+  if (do_rowsum) {
+    rs += __shfl_xor(rs, 1, 64);
+    const int m = m0 + srow;
+    if (sh == 0 && m < g.M) g.rowsum[(int64_t)bz * g.M + m] = rs;
+  }
+  if (slab_flip) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = -acc[i][j][r];
+  }
+  if constexpr (NP == 2) split_unscale(acc, inv_a, inv_b);
+  gemm_epilogue(g, acc, bz, m0, n0, wm, wn, li, lh);
+}
+
+// ---- host side: reserve LDS once per device, pick the instantiation, launch -------------------------------------------
+typedef void (*GemmKernel)(GemmArgs);
+// the four instantiations of a kernel template over two I/O-type flags, indexed a + 2 * b
+#define IO2_KERNELS(K) {&K<false, false>, &K<true, false>, &K<false, true>, &K<true, true>}
+
+// a dynamic-LDS request above 64 KiB has to be granted per kernel and device: `bytes` on every kernel of `ks`, once
+// per device (`once`: one per kernel family)
+inline int reserve_lds(PerDeviceOnce& once, std::initializer_list<GemmKernel> ks, size_t bytes, const char* what) {
+  if (!once.first()) return 0;
+  for (GemmKernel k : ks)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+      paradis_set_error("%s: cannot reserve LDS", what);
+      return 2;
+    }
+  return 0;
+}
+
+// KS = IO2_KERNELS(family): launch the instantiation that (a, b) selects; reserve_for: the name for the error message
+// if the family's `lds` bytes need reserving (on all four), nullptr if they fit the 64 KiB a kernel gets unasked
+template <const GemmKernel (&KS)[4]>
+int launch_io2(bool a, bool b, dim3 grid, dim3 block, size_t lds, const char* reserve_for, hipStream_t st, const GemmArgs& g) {
+  static PerDeviceOnce once;
+  if (reserve_for)
+    if (int e = reserve_lds(once, {KS[0], KS[1], KS[2], KS[3]}, lds, reserve_for)) return e;
+  hipLaunchKernelGGL(KS[a + 2 * b], grid, block, lds, st, g);
+  return 0;
+}
+}  // namespace

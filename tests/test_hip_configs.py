@@ -244,7 +244,7 @@ def test_cfg3_default_width_model_128x256_gradients_fp64_protocol():
     - the GPU GEMMs carry 8-10 u of zero-mean noise where oneDNN's blocked sums carry 3 (tools/gemm_bias_check.py), hence
     ~2 for both GPU arithmetics; what set the old bf16x3 apart was not its noise but an OFFSET shared by all outputs
     (the bf16 MFMA floors its accumulator when a k-tile's product sum outweighs it), which sums over pixels added up
-    coherently.  The checkerboard of negated-space blocks (csrc/gemm.hip) removes it; this test would catch its return.
+    coherently.  The checkerboard of negated-space blocks (csrc/gemm_common.h) removes it; this test would catch its return.
 
     Asserted: forward <= 1e-5 per seed; median over the seeds of the per-seed median ratio <= 3 and every per-seed
     median <= 4.5; at least two of the three seeds pass the single-seed bounds of tests/test_hip_model.py for EVERY
