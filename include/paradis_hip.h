@@ -393,6 +393,25 @@ int paradis_forcings(const int64_t* times_us /* [B,T] */, const double* lat_deg,
 int paradis_normalize_features(float* data, const int* kind, const float* p0, const float* p1,
                                int64_t rows, int C, float eps_q, int inverse, void* stream);
 
+/* ---- f5: forecast post-processing (reference trainer.py:772-778 = utils/postprocessing.py:190-215 de-normalisation
+ * + utils/postprocessing.py:74-122,143-187 Cartesian -> spherical winds, and the dew-point depression of
+ * utils/mhuaes.py:33-96 that utils/file_output.py:165-173 derives - all on the CPU there).  One pass: reads the
+ * normalised model output [B, C, H, W] (batch stride out_bs elements; never written) and writes the physical-unit
+ * state to chunk + chunk_off with batch stride chunk_bs (slot t of a [B, T, C, H, W] chunk: chunk_off = t*C*H*W),
+ * optionally the dew-point depression to dew + dew_off ([B, T, L, H, W]: dew_off = t*L*H*W; NULL to skip).
+ * DEVICE tables: kind / p0 / p1 [C] with the codes of the feature normalisation below; units [n_units][8] int =
+ * {type, q, T, x, y, z, level, 0}: type 0 one channel (its index in the q field), 1 a pressure level (channel indices
+ * of specific humidity - or -1 -, temperature, wind_x / wind_y / wind_z - x = -1: no wind conversion - and the level's
+ * index into plev), 2 the 10 m wind triple (x, y, z); every channel belongs to exactly one unit.  plev [n_levels]
+ * double, hPa.  trig: double sin(lat)[H], cos(lat)[H], sin(lon)[W], cos(lon)[W].  fp32 de-normalisation in the
+ * reference's operation order; winds and dew point in fp64, rounded once.  W % 4 == 0 and 16-byte aligned planes take
+ * the 16-byte path, anything else a scalar one with the same arithmetic.
+ * Algorithmic HBM bytes: 8*B*C*H*W (+ 4*B*L*H*W with the dew point). */
+int paradis_forecast_post(const float* output, int64_t out_bs, float* chunk, int64_t chunk_bs, int64_t chunk_off,
+                          float* dew, int64_t dew_bs, int64_t dew_off, const int* kind, const float* p0,
+                          const float* p1, float eps_q, const int* units, int n_units, const double* plev,
+                          int n_levels, const double* trig, int B, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

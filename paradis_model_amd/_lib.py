@@ -106,6 +106,7 @@ SIGNATURES = {
     "paradis_amse_tables": (I, [P, P, P, I, I, P]),
     "paradis_amse_ws_bytes": (S, [I, I]),
     "paradis_amse_loss": (I, [P, P, P, P, P, P, P, I, I, I, P]),
+    "paradis_forecast_post": (I, [P, L, P, L, L, P, L, L, P, P, P, F, P, I, P, I, P, I, I, I, I, P]),
 }
 
 _missing = []

@@ -256,6 +256,51 @@ class GraphedTrainStep:
         return loss
 
 
+# ---------------------------------------------------------------------------------- graphed forward
+def capture_forward(fn, warmup: int = 2):
+    """Capture the no-grad callable ``fn()`` into a HIP graph: ``warmup`` eager calls on a side stream (kernel attributes,
+    lazily built geometry and the allocator's pools must exist before capture), then one captured call.  Returns
+    (graph, what the captured call returned - static tensors in the graph's pool, overwritten by every replay).
+    Capture mode as ``GraphedTrainStep``: "global" unless a process group is alive."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(max(1, warmup)):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    with_pg = dist.is_available() and dist.is_initialized()
+    if with_pg:
+        import time as _time
+        _time.sleep(0.25)            # see GraphedTrainStep: let RCCL's watchdog retire its work items first
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local" if with_pg else "global"):
+        out = fn()
+    return graph, out
+
+
+class GraphedForward:
+    """The no-grad forward of ``model`` on inputs shaped like ``example_input`` as one HIP-graph replay (one host call
+    instead of one per kernel: what a host-bound small-batch forward needs).  ``__call__(x) -> y``; ``y`` is
+    a static tensor that the next call overwrites.  Captured outside ``ops.frozen_weights()``: the weight-image kernels
+    are nodes of the graph, so parameters written in place (``load_state_dict``, an optimiser step) are honoured by the
+    next replay without re-capture.  Works under ``torch.no_grad()`` and ``torch.inference_mode()``: the static tensors
+    are created outside inference mode."""
+
+    def __init__(self, model, example_input, warmup: int = 2):
+        from . import ops
+        self.model = model
+        with torch.inference_mode(False), torch.no_grad(), ops.frozen_weights(False):
+            self.static_input = torch.empty_like(example_input).copy_(example_input)
+            self.graph, self.static_output = capture_forward(lambda: model(self.static_input), warmup)
+
+    def __call__(self, x):
+        if x.data_ptr() != self.static_input.data_ptr():
+            self.static_input.copy_(x, non_blocking=True)
+        self.graph.replay()
+        return self.static_output
+
+
 # ---------------------------------------------------------------------------------- data parallel
 def init_distributed(backend: Optional[str] = None, capturable: bool = False) -> Tuple[int, int, int]:
     """(rank, local_rank, world) from the torchrun environment; no-op for a single process.
