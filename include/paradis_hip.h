@@ -55,7 +55,7 @@ extern "C" {
 #define PARADIS_ADVECT_HALO_BWD_SHIFT 16
 #define PARADIS_ADVECT_HALO(h) (((h) + 1) << PARADIS_ADVECT_HALO_SHIFT)
 
-int paradis_abi_version(void);   /* 9: bf16-stored tensors of the bf16-mixed mode (paradis_pw_gemm_fwd16 / _dgrad16 / _wgrad16, paradis_bias_grads16, paradis_channel_norm_fwd16 / _bwd16, paradis_dwconv_geo_fwd16 / _bwd16, paradis_act_bwd16): additions only; 8: PARADIS_GEMM_BF16 scheme, paradis_pw_gemm_wgrad_slabs (query); no signature changed; 7: paradis_dwconv_geo_dgrad_add, paradis_dwconv_geo_bwd, paradis_pw_gemm_split_weights_pair, paradis_pw_gemm_fwd_gated, paradis_gated_blend_bwd_out; 6: paradis_sl_advect_ws_bytes takes the call's flags (strip schedule); 5: no amax side outputs, lat_cells table of sl_advect_* (4: GEMM `scheme` arguments, paradis_amax_partials; 3: `flags` of sl_advect_*) */
+int paradis_abi_version(void);   /* 10: paradis_adamw_step_d / paradis_adamw_multi_d (hyper-parameters in double): additions only; 9: bf16-stored tensors of the bf16-mixed mode (paradis_pw_gemm_fwd16 / _dgrad16 / _wgrad16, paradis_bias_grads16, paradis_channel_norm_fwd16 / _bwd16, paradis_dwconv_geo_fwd16 / _bwd16, paradis_act_bwd16): additions only; 8: PARADIS_GEMM_BF16 scheme, paradis_pw_gemm_wgrad_slabs (query); no signature changed; 7: paradis_dwconv_geo_dgrad_add, paradis_dwconv_geo_bwd, paradis_pw_gemm_split_weights_pair, paradis_pw_gemm_fwd_gated, paradis_gated_blend_bwd_out; 6: paradis_sl_advect_ws_bytes takes the call's flags (strip schedule); 5: no amax side outputs, lat_cells table of sl_advect_* (4: GEMM `scheme` arguments, paradis_amax_partials; 3: `flags` of sl_advect_*) */
 const char* paradis_last_error(void);
 
 /* ---- a1: GeoCyclicPadding.forward (reference model/padding.py:11-39) and its adjoint.
@@ -113,7 +113,10 @@ size_t paradis_dwconv_geo_wgrad_ws_bytes(int B, int C, int H, int W, int k);
 int paradis_dwconv_geo_wgrad(const float* gy, const float* x, float* gw, float* gbias,
                              int B, int C, int H, int W, int k, void* workspace, void* stream);
 
-/* ---- a11: PhysicalDownsample (reference model/blocks.py:57-71): geocyclic 5x5 box mean, stride s */
+/* ---- a11: PhysicalDownsample (reference model/blocks.py:57-71): geocyclic 5x5 box mean, stride s >= 1;
+ * y [planes, (H-1)/s + 1, (W-1)/s + 1].  Restriction: H >= 4 and W >= 4, W even (rc 1 otherwise).  The reference module
+ * also runs at H = 3 (its halo rows then mirror through the opposite pole row) and at W = 2 (the wrap repeats the
+ * plane); neither is a grid the model is built on, and the index map of a1 (pad <= H - 2) does not cover them. */
 int paradis_avgpool_geo_fwd(const float* x, float* y, int64_t planes, int H, int W, int stride, void* stream);
 int paradis_avgpool_geo_bwd(const float* gy, float* gx, int64_t planes, int H, int W, int stride, void* stream);
 
@@ -340,6 +343,15 @@ int paradis_adamw_multi(const int64_t* ptrs, const int64_t* numel, const int* ch
                         const int64_t* chunk_off, int n_tensors, int n_chunks, float lr, float beta1,
                         float beta2, float eps, float weight_decay, int step, const int* dev_state, void* stream);
 int paradis_adamw_tick(int* dev_state, void* stream);
+/* The same two updates with the hyper-parameters in double, as torch.optim.AdamW holds them (ABI 10): the coefficients
+ * 1 - lr*weight_decay, 1 - beta1, 1 - beta2, lr / (1 - beta1^step) and sqrt(1 - beta2^step) are formed in double and
+ * rounded to fp32 once - the scalars torch hands its fp32 kernels.  The float entry points above widen their arguments
+ * and call these: with beta1 = 0.9f they update with 1 - beta1 = 0.10000002, 2.4e-7 off torch's 0.1f in m (and v). */
+int paradis_adamw_step_d(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1,
+                         double beta2, double eps, double weight_decay, int step, void* stream);
+int paradis_adamw_multi_d(const int64_t* ptrs, const int64_t* numel, const int* chunk_tensor,
+                          const int64_t* chunk_off, int n_tensors, int n_chunks, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, int step, const int* dev_state, void* stream);
 
 /* ---- f1 (AMSE): the spectral loss of reference utils/amse_loss.py on the equiangular grid H x W, W = 2(H-1), poles
  * included; row j of a plane is colatitude pi*j/(H-1) (RealSHT's order).  M = H-1 degrees / orders are used.

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -24,7 +24,7 @@ if not os.path.exists(LIB_PATH):
 
 lib = ctypes.CDLL(LIB_PATH)
 
-P, I, L, F, S = c_void_p, c_int, c_int64, c_float, c_size_t
+P, I, L, F, S, D = c_void_p, c_int, c_int64, c_float, c_size_t, c_double
 
 # name -> (restype, argtypes); mirrors include/paradis_hip.h one to one
 SIGNATURES = {
@@ -101,6 +101,8 @@ SIGNATURES = {
     "paradis_adamw_chunk": (I, []),
     "paradis_adamw_multi": (I, [P, P, P, P, I, I, F, F, F, F, F, I, P, P]),
     "paradis_adamw_tick": (I, [P, P]),
+    "paradis_adamw_step_d": (I, [P, P, P, P, L, D, D, D, D, D, I, P]),
+    "paradis_adamw_multi_d": (I, [P, P, P, P, I, I, D, D, D, D, D, I, P, P]),
     "paradis_amse_table_floats": (S, [I]),
     "paradis_amse_tables_ws_bytes": (S, [I]),
     "paradis_amse_tables": (I, [P, P, P, I, I, P]),

@@ -4,6 +4,12 @@
 // axis (coalesced 256-B rows) and waves split the channel axis.  HBM-bound: 8 B per (c, pixel)
 // forward.  The input may be the virtual concatenation of two tensors (reference
 // model/paradis.py:249, cat([hidden, hidden_static])) so the cat is never materialised.
+//
+// Centre of the normalisation: the fp32 mean m (the `mean` output) carries a rounding error of up to ulp(m)/2, which a
+// channel spread far below |m| does not forgive (x = 100 +- 0.01: xhat 4e-4 off, y and gx 1e-3 - the fp32 ATen module has
+// the same error).  The differences d = x - m are exact there, so the residual delta = sum_c d / C of the true mean is
+// formed from them and  xhat = (d - delta) rstd,  var = (sum d^2 - delta sum d) / (C-1)  (the shifted-data form of the
+// same two-pass definition).  Forward and the streaming backward both do; `mean` stays the fp32 mean.
 #include <algorithm>
 #include "common.h"
 
@@ -38,7 +44,8 @@ channel_norm_fwd_kernel(CatSrc s, const float* __restrict__ w, const float* __re
                         float* __restrict__ rstd_out, int P, int tiles, float eps) {
   constexpr int G = 1024 / NPXF;
   __shared__ float red[G][NPXF];
-  __shared__ float stat[2][NPXF];
+  __shared__ float red2[G][NPXF];
+  __shared__ float stat[3][NPXF];
   const int C = s.C1 + s.C2;
   const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * NPXF;
   const int lane = threadIdx.x % NPXF, grp = threadIdx.x / NPXF;
@@ -67,37 +74,42 @@ channel_norm_fwd_kernel(CatSrc s, const float* __restrict__ w, const float* __re
   }
   __syncthreads();
   const float mean = stat[0][lane];
-  float sq = 0.f;
+  float sq = 0.f, sd = 0.f;
   if (MAXV > 0) {
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
       const int c = grp + G * i;
       const float d = (c < C) ? vals[i] - mean : 0.f;
       sq += d * d;
+      sd += d;
     }
   } else {
     for (int c = grp; c < C; c += G) {
       const float d = live ? s.row(b, c, P)[p] - mean : 0.f;
       sq += d * d;
+      sd += d;
     }
   }
   __syncthreads();
   red[grp][lane] = sq;
+  red2[grp][lane] = sd;
   __syncthreads();
   if (grp == 0) {
-    float t = 0.f;
+    float t = 0.f, u = 0.f;
 #pragma unroll
-    for (int k = 0; k < G; ++k) t += red[k][lane];
-    const float var = t / (float)(C - 1);
+    for (int k = 0; k < G; ++k) { t += red[k][lane]; u += red2[k][lane]; }
+    const float delta = u / (float)C;                               // residual of the true mean (see the file header)
+    const float var = fmaxf(t - delta * u, 0.f) / (float)(C - 1);
     const float r = 1.0f / sqrtf(var + eps);
     stat[1][lane] = r;
+    stat[2][lane] = delta;
     if (live) {
       mean_out[(int64_t)b * P + p] = mean;
       rstd_out[(int64_t)b * P + p] = r;
     }
   }
   __syncthreads();
-  const float rstd = stat[1][lane];
+  const float rstd = stat[1][lane], delta = stat[2][lane];
   if (live) {
     float* yb = y + (int64_t)b * C * P + p;
     uint16_t* yb16 = reinterpret_cast<uint16_t*>(y) + (int64_t)b * C * P + p;
@@ -106,13 +118,13 @@ channel_norm_fwd_kernel(CatSrc s, const float* __restrict__ w, const float* __re
       for (int i = 0; i < MAXV; ++i) {
         const int c = grp + G * i;
         if (c < C) {
-          const float v = (vals[i] - mean) * rstd * w[c] + bias[c];
+          const float v = ((vals[i] - mean) - delta) * rstd * w[c] + bias[c];
           if constexpr (Y16) yb16[(int64_t)c * P] = bf16_bits(v); else yb[(int64_t)c * P] = v;
         }
       }
     } else {
       for (int c = grp; c < C; c += G) {
-        const float v = (s.row(b, c, P)[p] - mean) * rstd * w[c] + bias[c];
+        const float v = ((s.row(b, c, P)[p] - mean) - delta) * rstd * w[c] + bias[c];
         if constexpr (Y16) yb16[(int64_t)c * P] = bf16_bits(v); else yb[(int64_t)c * P] = v;
       }
     }
@@ -131,7 +143,8 @@ channel_norm_fwd32_kernel(CatSrc s, const float* __restrict__ w, const float* __
                           int P, int tiles, float eps) {
   constexpr int G = 32, NPXF = 32;
   __shared__ float red[G][NPXF];
-  __shared__ float stat[2][NPXF];
+  __shared__ float red2[G][NPXF];
+  __shared__ float stat[3][NPXF];
   __shared__ float wl[G * MAXV], bl[G * MAXV];
   const int C = s.C1 + s.C2;
   const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * NPXF;
@@ -167,28 +180,32 @@ channel_norm_fwd32_kernel(CatSrc s, const float* __restrict__ w, const float* __
   }
   __syncthreads();
   const float mean = stat[0][lane];
-  float sq = 0.f;
+  float sq = 0.f, sd = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
     const float d = (2 * wave + G * i < C) ? vals[i] - mean : 0.f;
     sq += d * d;
+    sd += d;
   }
   __syncthreads();
   red[grp][lane] = sq;
+  red2[grp][lane] = sd;
   __syncthreads();
   if (grp == 0) {
-    float t = 0.f;
+    float t = 0.f, u = 0.f;
 #pragma unroll
-    for (int k = 0; k < G; ++k) t += red[k][lane];
-    const float r = 1.0f / sqrtf(t / (float)(C - 1) + eps);
+    for (int k = 0; k < G; ++k) { t += red[k][lane]; u += red2[k][lane]; }
+    const float delta = u / (float)C;                               // residual of the true mean (see the file header)
+    const float r = 1.0f / sqrtf(fmaxf(t - delta * u, 0.f) / (float)(C - 1) + eps);
     stat[1][lane] = r;
+    stat[2][lane] = delta;
     if (live) {
       mean_out[(int64_t)b * P + p] = mean;
       rstd_out[(int64_t)b * P + p] = r;
     }
   }
   __syncthreads();
-  const float rstd = stat[1][lane];
+  const float rstd = stat[1][lane], delta = stat[2][lane];
   if (!live) return;
   typedef __attribute__((address_space(1))) float* gwptr;
   typedef __attribute__((address_space(1))) uint16_t* gwptr16;
@@ -199,7 +216,7 @@ channel_norm_fwd32_kernel(CatSrc s, const float* __restrict__ w, const float* __
     const int ce = 2 * wave + G * i;
     if (ce < C) {
       const int c = grp + G * i;
-      const float v = (vals[i] - mean) * rstd * wl[c] + bl[c];
+      const float v = ((vals[i] - mean) - delta) * rstd * wl[c] + bl[c];
       const uint64_t a = ybase + (uint64_t)ce * P * ES;
       const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
       if constexpr (Y16) ((gwptr16)(((uint64_t)hi << 32) | lo))[voff] = bf16_bits(v);
@@ -487,8 +504,9 @@ template <bool GY16>
 __global__ void __launch_bounds__(NSTAT_PX * NSTAT_G)
 channel_norm_bwd_stats_kernel(const float* __restrict__ gy, CatSrc s, const float* __restrict__ w,
                               const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-                              float* __restrict__ m1_out, float* __restrict__ m2_out, int P, int tiles) {
-  __shared__ float red[2][NSTAT_G][NSTAT_PX];
+                              float* __restrict__ m1_out, float* __restrict__ m2_out, float* __restrict__ dl_out,
+                              int P, int tiles) {
+  __shared__ float red[3][NSTAT_G][NSTAT_PX];
   const int C = s.C1 + s.C2;
   const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * NSTAT_PX;
   const int lane = threadIdx.x & 63;
@@ -497,7 +515,7 @@ channel_norm_bwd_stats_kernel(const float* __restrict__ gy, CatSrc s, const floa
   const float mean = mean_in[(int64_t)b * P + p], rstd = rstd_in[(int64_t)b * P + p];
   const float* gyb = gy + (int64_t)b * C * P + p;
   [[maybe_unused]] const uint16_t* gyb16 = reinterpret_cast<const uint16_t*>(gy) + (int64_t)b * C * P + p;
-  float s1 = 0.f, s2 = 0.f;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   for (int c0 = grp; c0 < C; c0 += NSTAT_G * NSTAT_U) {
     float gv[NSTAT_U], xv[NSTAT_U], wv[NSTAT_U];
 #pragma unroll
@@ -510,17 +528,26 @@ channel_norm_bwd_stats_kernel(const float* __restrict__ gy, CatSrc s, const floa
 #pragma unroll
     for (int j = 0; j < NSTAT_U; ++j) {
       const float gh = gv[j] * wv[j];
+      const float d = xv[j] - mean;
+      s0 += c0 + NSTAT_G * j < C ? d : 0.f;
       s1 += gh;
-      s2 += gh * ((xv[j] - mean) * rstd);
+      s2 += gh * (d * rstd);
     }
   }
-  red[0][grp][lane] = s1;
-  red[1][grp][lane] = s2;
+  red[0][grp][lane] = s0;
+  red[1][grp][lane] = s1;
+  red[2][grp][lane] = s2;
   __syncthreads();
-  if (grp < 2 && p0 + lane < P) {
-    const float t = (red[grp][0][lane] + red[grp][1][lane]) + (red[grp][2][lane] + red[grp][3][lane]);
-    if (grp == 0) m1_out[(int64_t)b * P + p] = t / (float)C;
-    else m2_out[(int64_t)b * P + p] = t / (float)(C - 1);
+  if (grp == 0 && p0 + lane < P) {
+    float t[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t[k] = (red[k][0][lane] + red[k][1][lane]) + (red[k][2][lane] + red[k][3][lane]);
+    // xhat = (x - mean) rstd - dl with dl = rstd delta, delta = sum_c (x - mean) / C: the residual of the true mean (file
+    // header); s2 was summed against the uncorrected xhat and is linear in the shift
+    const float dl = t[0] / (float)C * rstd;
+    m1_out[(int64_t)b * P + p] = t[1] / (float)C;
+    m2_out[(int64_t)b * P + p] = (t[2] - dl * t[1]) / (float)(C - 1);
+    dl_out[(int64_t)b * P + p] = dl;
   }
 }
 
@@ -531,6 +558,7 @@ __global__ void __launch_bounds__(256)
 channel_norm_bwd_apply_kernel(const float* __restrict__ gy, CatSrc s, const float* __restrict__ w,
                               const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
                               const float* __restrict__ m1_in, const float* __restrict__ m2_in,
+                              const float* __restrict__ dl_in,
                               float* __restrict__ gx1, float* __restrict__ gx2, int64_t gbs1, int64_t gbs2,
                               const float* __restrict__ add1, int64_t abs1, float* __restrict__ partial,
                               int P, int span, int chunks) {
@@ -550,6 +578,7 @@ channel_norm_bwd_apply_kernel(const float* __restrict__ gy, CatSrc s, const floa
   const float* rstd = rstd_in + (int64_t)b * P;
   const float* m1 = m1_in + (int64_t)b * P;
   const float* m2 = m2_in + (int64_t)b * P;
+  const float* dl = dl_in + (int64_t)b * P;
   const float wc = w[c];
   float a = 0.f, d = 0.f;
   if (VEC) {
@@ -564,10 +593,11 @@ channel_norm_bwd_apply_kernel(const float* __restrict__ gy, CatSrc s, const floa
       const float4 xv = *reinterpret_cast<const float4*>(x + q);
       const float4 mu = *reinterpret_cast<const float4*>(mean + q), rs = *reinterpret_cast<const float4*>(rstd + q);
       const float4 a1 = *reinterpret_cast<const float4*>(m1 + q), a2 = *reinterpret_cast<const float4*>(m2 + q);
+      const float4 dv = *reinterpret_cast<const float4*>(dl + q);
       float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ad) av = *reinterpret_cast<const float4*>(ad + q);
-      const float xh0 = (xv.x - mu.x) * rs.x, xh1 = (xv.y - mu.y) * rs.y, xh2 = (xv.z - mu.z) * rs.z,
-                  xh3 = (xv.w - mu.w) * rs.w;
+      const float xh0 = (xv.x - mu.x) * rs.x - dv.x, xh1 = (xv.y - mu.y) * rs.y - dv.y, xh2 = (xv.z - mu.z) * rs.z - dv.z,
+                  xh3 = (xv.w - mu.w) * rs.w - dv.w;
       a += (gv.x * xh0 + gv.y * xh1) + (gv.z * xh2 + gv.w * xh3);
       d += (gv.x + gv.y) + (gv.z + gv.w);
       if (out) {
@@ -581,7 +611,7 @@ channel_norm_bwd_apply_kernel(const float* __restrict__ gy, CatSrc s, const floa
     }
   } else {
     for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
-      const float gv = GY16 ? bf16_widen(g16[q]) : g[q], xh = (x[q] - mean[q]) * rstd[q];
+      const float gv = GY16 ? bf16_widen(g16[q]) : g[q], xh = (x[q] - mean[q]) * rstd[q] - dl[q];
       a += gv * xh;
       d += gv;
       if (out) out[q] = rstd[q] * (gv * wc - m1[q] - xh * m2[q]) + (ad ? ad[q] : 0.f);
@@ -715,7 +745,7 @@ extern "C" size_t paradis_channel_norm_bwd_ws_bytes(int B, int C, int P) {
   const size_t nblk = b * ((P + 31) / 32);
   const size_t fused = (nblk + (nblk + 63) / 64) * 2 * C * sizeof(float);   // per-block partials + per-chunk sums
   const size_t nrow = b * ((P + APPLY_SPAN - 1) / APPLY_SPAN);
-  const size_t streaming = (2 * b * P + (nrow + (nrow + 63) / 64) * 2 * C) * sizeof(float);
+  const size_t streaming = (3 * b * P + (nrow + (nrow + 63) / 64) * 2 * C) * sizeof(float);
   return std::max({three_kernel, fused, streaming}) + 256;
 }
 
@@ -750,7 +780,8 @@ static int channel_norm_bwd_impl(const float* gy, const float* x1, const float* 
   if (norm_bwd_streaming(B, C, P)) {
     float* m1 = (float*)workspace;
     float* m2 = m1 + (size_t)B * P;
-    float* partial = m2 + (size_t)B * P;
+    float* dl = m2 + (size_t)B * P;
+    float* partial = dl + (size_t)B * P;
     const int tiles = (P + NSTAT_PX - 1) / NSTAT_PX;
     auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const bool vec = P % 4 == 0 && x1_bs % 4 == 0 && (C2 == 0 || (x2_bs % 4 == 0 && a16(x2))) && gx1_bs % 4 == 0 &&
@@ -761,15 +792,15 @@ static int channel_norm_bwd_impl(const float* gy, const float* x1, const float* 
     //  Measured, removed: 318 us per call in one chunk, 371 / 424 / 600 / 1338 us with read sets of 160 / 96 / 48 / 24 MB per
     //  chunk at 32 x 64, B = 32, C = 1024; the training step 152.7 -> 156.5 / 163.8 ms.  profiles/r06_norm_bwd_chunked.txt)
     hipLaunchKernelGGL(channel_norm_bwd_stats_kernel<GY16>, dim3((unsigned)((int64_t)B * tiles)), dim3(NSTAT_PX * NSTAT_G), 0,
-                       st, gy, s, w, mean, rstd, m1, m2, P, tiles);
+                       st, gy, s, w, mean, rstd, m1, m2, dl, P, tiles);
     const unsigned grid = (unsigned)((int64_t)B * C * apply_chunks);
     if (vec)
       hipLaunchKernelGGL((channel_norm_bwd_apply_kernel<true, GY16>), dim3(grid), dim3(256), 0, st, gy, s, w, mean, rstd,
-                         (const float*)m1, (const float*)m2, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
+                         (const float*)m1, (const float*)m2, (const float*)dl, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
                          APPLY_SPAN, apply_chunks);
     else
       hipLaunchKernelGGL((channel_norm_bwd_apply_kernel<false, GY16>), dim3(grid), dim3(256), 0, st, gy, s, w, mean, rstd,
-                         (const float*)m1, (const float*)m2, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
+                         (const float*)m1, (const float*)m2, (const float*)dl, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
                          APPLY_SPAN, apply_chunks);
     nblk = B * apply_chunks;
     const int rows = 64, chunks = (nblk + rows - 1) / rows;
@@ -785,6 +816,7 @@ static int channel_norm_bwd_impl(const float* gy, const float* x1, const float* 
     paradis_set_error("channel_norm_bwd16: shape outside the streaming kernels (paradis_channel_norm_bwd16_ok)");
     return 1;
   } else {
+  // (the kernels below - A/B builds with NORM_BWD_STREAMING = 0 - centre on the fp32 mean alone: file header)
   if (C <= 32 * 36 && (int64_t)B * ((P + 31) / 32) < (1ll << 31)) {
     // g_norm_bwd_reread: 1 = stream-twice kernel (default; in the training step 231.6 vs 235.2 ms),
     // 0 = gy in registers + xhat in LDS, one workgroup per CU (half the HBM traffic, phases serialised).

@@ -78,53 +78,75 @@ copy_channels_kernel(const float* __restrict__ src, int64_t src_bs, float* __res
   }
 }
 
-// torch.optim.AdamW, single tensor, same operation order as the ATen implementation:
+// torch.optim.AdamW, same operation order as the ATen implementation:
 //   p *= 1 - lr*wd;  m = lerp(m, g, 1-b1);  v = b2*v + (1-b2)*g*g;
 //   denom = sqrt(v)/sqrt(bc2) + eps;  p -= (lr/bc1) * m / denom
+// The scalar coefficients are what torch hands its fp32 kernels: formed in DOUBLE from the double hyper-parameters and
+// rounded once (1 - 0.9 -> 0.1f).  Formed in fp32 from fp32-rounded betas, 1.0f - 0.9f = 0.10000002 is 2.4e-7 off, and so
+// were m and v after every step (tests/test_hip_kernel_edges.py::test_adamw).
+struct AdamWCoef { float decay, omb1, b2, omb2, eps, step_size, bc2_sqrt; };
+
+AdamWCoef adamw_coef(double lr, double b1, double b2, double eps, double wd, int step) {
+  const int st = step >= 1 ? step : 1;
+  lr = (double)(float)lr;     // the device-state path holds lr as fp32 bits: both paths form the same coefficients, bit for bit
+  AdamWCoef k;
+  k.decay = (float)(1.0 - lr * wd);
+  k.omb1 = (float)(1.0 - b1);
+  k.b2 = (float)b2;
+  k.omb2 = (float)(1.0 - b2);
+  k.eps = (float)eps;
+  k.step_size = (float)(lr / (1.0 - pow(b1, st)));
+  k.bc2_sqrt = (float)sqrt(1.0 - pow(b2, st));
+  return k;
+}
+
+__device__ __forceinline__ void adamw_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                             float* __restrict__ v, int64_t i, const AdamWCoef& k) {
+  const float gi = g[i];
+  float pi = p[i] * k.decay;
+  float mi = m[i];
+  mi = mi + k.omb1 * (gi - mi);
+  const float vi = k.b2 * v[i] + k.omb2 * gi * gi;
+  const float denom = sqrtf(vi) / k.bc2_sqrt + k.eps;
+  pi = pi - k.step_size * (mi / denom);
+  p[i] = pi; m[i] = mi; v[i] = vi;
+}
+
 __global__ void __launch_bounds__(256)
 adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-             float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps, float wd,
-             float bc1, float bc2_sqrt) {
-  const float step_size = lr / bc1;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const float gi = g[i];
-    float pi = p[i] * (1.0f - lr * wd);
-    float mi = m[i];
-    mi = mi + (1.0f - b1) * (gi - mi);
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi = pi - step_size * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
+             float* __restrict__ v, int64_t n, AdamWCoef k) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    adamw_update(p, g, m, v, i, k);
 }
 
 // One launch for a whole parameter group: block c works on chunk c = (tensor index, offset); all
 // tensors share the hyper-parameters and the step count.  (335 per-tensor launches of ~5 us are
 // launch-bound: 0.7 % of the training step.)
 constexpr int ADAMW_CHUNK = 32768;
-// dev (optional): {step count as float bits are NOT used - int32 step at [0], float lr at [1]} kept on the device so
+// dev (optional): {int32 step at [0], the bits of the fp32 lr at [1]} kept on the device so
 // that a captured HIP graph of the training step stays valid from one replay to the next (the host-side step
-// count and learning rate would be frozen into the kernel arguments): the bias corrections are then formed
-// here, in double like the host path.
+// count and learning rate would be frozen into the kernel arguments): the coefficients that depend on them are then
+// formed here, in double like the host path.
 __global__ void __launch_bounds__(256)
 adamw_multi_kernel(const int64_t* __restrict__ ptrs /* [4][T]: p, g, m, v */, const int64_t* __restrict__ numel,
                    const int* __restrict__ chunk_tensor, const int64_t* __restrict__ chunk_off, int T,
-                   float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                   const int* __restrict__ dev) {
+                   AdamWCoef k, double b1, double b2, double wd, const int* __restrict__ dev) {
   if (dev) {     // (workgroup-uniform)
-    // one thread forms the bias corrections (two double pow + a sqrt), the workgroup reads them from LDS.  Same formula
+    // one thread forms the coefficients (two double pow + a sqrt), the workgroup reads them from LDS.  Same formulas
     // in double as the host path; the device's pow is not guaranteed to round like the host's libm, so the two paths
-    // agree to ~1 ulp of the fp32 corrections, not bit for bit (tests/test_hip_train_rows.py checks 1e-6).
-    __shared__ float bc[2];
+    // agree to ~1 ulp of the fp32 coefficients, not bit for bit (tests/test_hip_train_rows.py checks 1e-6).
+    __shared__ float co[3];
     if (threadIdx.x == 0) {
       const int step = dev[0];
-      bc[0] = (float)(1.0 - pow((double)b1, (double)step));
-      bc[1] = (float)sqrt(1.0 - pow((double)b2, (double)step));
+      const double lr = (double)__int_as_float(dev[1]);
+      co[0] = (float)(1.0 - lr * wd);
+      co[1] = (float)(lr / (1.0 - pow(b1, (double)step)));
+      co[2] = (float)sqrt(1.0 - pow(b2, (double)step));
     }
     __syncthreads();
-    lr = __int_as_float(dev[1]);
-    bc1 = bc[0];
-    bc2_sqrt = bc[1];
+    k.decay = co[0];
+    k.step_size = co[1];
+    k.bc2_sqrt = co[2];
   }
   const int t = chunk_tensor[blockIdx.x];
   const int64_t off = chunk_off[blockIdx.x];
@@ -133,17 +155,7 @@ adamw_multi_kernel(const int64_t* __restrict__ ptrs /* [4][T]: p, g, m, v */, co
   const float* g = reinterpret_cast<const float*>(ptrs[T + t]) + off;
   float* m = reinterpret_cast<float*>(ptrs[2 * T + t]) + off;
   float* v = reinterpret_cast<float*>(ptrs[3 * T + t]) + off;
-  const float step_size = lr / bc1;
-  for (int64_t i = threadIdx.x; i < n; i += 256) {
-    const float gi = g[i];
-    float pi = p[i] * (1.0f - lr * wd);
-    float mi = m[i];
-    mi = mi + (1.0f - b1) * (gi - mi);
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    pi = pi - step_size * (mi / denom);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-  }
+  for (int64_t i = threadIdx.x; i < n; i += 256) adamw_update(p, g, m, v, i, k);
 }
 
 __global__ void adamw_tick_kernel(int* __restrict__ dev) { dev[0] += 1; }
@@ -193,20 +205,26 @@ extern "C" int paradis_copy_channels(const float* src, int64_t src_bs, float* ds
 
 extern "C" int paradis_adamw_chunk(void) { return ADAMW_CHUNK; }
 
+extern "C" int paradis_adamw_multi_d(const int64_t* ptrs, const int64_t* numel, const int* chunk_tensor,
+                                     const int64_t* chunk_off, int n_tensors, int n_chunks, double lr,
+                                     double beta1, double beta2, double eps, double weight_decay, int step,
+                                     const int* dev_state, void* stream) {
+  PD_REQUIRE(n_tensors >= 0 && n_chunks >= 0 && (step >= 1 || dev_state != nullptr), "adamw_multi: bad arguments");
+  if (n_chunks == 0) return 0;
+  PD_REQUIRE(ptrs && numel && chunk_tensor && chunk_off, "adamw_multi: tables missing");
+  hipLaunchKernelGGL(adamw_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, ptrs, numel,
+                     chunk_tensor, chunk_off, n_tensors, adamw_coef(lr, beta1, beta2, eps, weight_decay, step), beta1,
+                     beta2, weight_decay, dev_state);
+  PD_CHECK_LAUNCH("adamw_multi");
+  return 0;
+}
+
 extern "C" int paradis_adamw_multi(const int64_t* ptrs, const int64_t* numel, const int* chunk_tensor,
                                    const int64_t* chunk_off, int n_tensors, int n_chunks, float lr,
                                    float beta1, float beta2, float eps, float weight_decay, int step,
                                    const int* dev_state, void* stream) {
-  PD_REQUIRE(n_tensors >= 0 && n_chunks >= 0 && (step >= 1 || dev_state != nullptr), "adamw_multi: bad arguments");
-  if (n_chunks == 0) return 0;
-  PD_REQUIRE(ptrs && numel && chunk_tensor && chunk_off, "adamw_multi: tables missing");
-  const int st = step >= 1 ? step : 1;
-  const float bc1 = (float)(1.0 - pow((double)beta1, st));
-  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, st));
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, ptrs, numel,
-                     chunk_tensor, chunk_off, n_tensors, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, dev_state);
-  PD_CHECK_LAUNCH("adamw_multi");
-  return 0;
+  return paradis_adamw_multi_d(ptrs, numel, chunk_tensor, chunk_off, n_tensors, n_chunks, lr, beta1, beta2, eps,
+                               weight_decay, step, dev_state, stream);
 }
 
 // dev_state[0] += 1 on the stream (the step count of a captured training step lives on the device)
@@ -217,15 +235,19 @@ extern "C" int paradis_adamw_tick(int* dev_state, void* stream) {
   return 0;
 }
 
+extern "C" int paradis_adamw_step_d(float* p, const float* g, float* m, float* v, int64_t n, double lr,
+                                    double beta1, double beta2, double eps, double weight_decay, int step,
+                                    void* stream) {
+  PD_REQUIRE(n >= 0 && step >= 1, "adamw_step: bad arguments");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     adamw_coef(lr, beta1, beta2, eps, weight_decay, step));
+  PD_CHECK_LAUNCH("adamw_step");
+  return 0;
+}
+
 extern "C" int paradis_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr,
                                   float beta1, float beta2, float eps, float weight_decay, int step,
                                   void* stream) {
-  PD_REQUIRE(n >= 0 && step >= 1, "adamw_step: bad arguments");
-  if (n == 0) return 0;
-  const float bc1 = (float)(1.0 - pow((double)beta1, step));
-  const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
-                     beta1, beta2, eps, weight_decay, bc1, bc2_sqrt);
-  PD_CHECK_LAUNCH("adamw_step");
-  return 0;
+  return paradis_adamw_step_d(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, stream);
 }

@@ -12,7 +12,7 @@ from ._lib import check, dptr, lib, require_hip, stream_ptr
 
 class AdamW(torch.optim.Optimizer):
     """``capturable=True``: the step count and the learning rate of every group also live on the device
-    (``paradis_adamw_multi(..., dev_state)``), so a HIP graph captured around ``step()`` stays valid from replay to
+    (``paradis_adamw_multi_d(..., dev_state)``), so a HIP graph captured around ``step()`` stays valid from replay to
     replay (``harness.GraphedTrainStep``); same formula, the bias corrections formed in double on the device (agrees with the
     host-side path to ~1 ulp of the fp32 corrections: the device pow is not the host libm, test bound 1e-6)."""
 
@@ -83,7 +83,7 @@ class AdamW(torch.optim.Optimizer):
             for p in params:
                 state = self.state[p]
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                check(lib.paradis_adamw_step(dptr(p), dptr(g), dptr(state["exp_avg"]),
+                check(lib.paradis_adamw_step_d(dptr(p), dptr(g), dptr(state["exp_avg"]),
                                              dptr(state["exp_avg_sq"]), p.numel(), group["lr"], b1, b2,
                                              group["eps"], group["weight_decay"], int(state["step"]), st),
                       "adamw_step")
@@ -104,7 +104,7 @@ class AdamW(torch.optim.Optimizer):
                 c["host"].copy_(t)
 
     def _step_group_fused(self, gi, group, params, step, st):
-        """One launch for the group (``paradis_adamw_multi``).  Only the chunk list (a function of the
+        """One launch for the group (``paradis_adamw_multi_d``).  Only the chunk list (a function of the
         parameter sizes) is cached; the four address rows (parameter, gradient, both moments) are
         rewritten every step - ``load_state_dict``, ``p.data = ...`` or ``model.to()`` replace tensors
         behind the same parameter ids - and reach the device through a pinned staging buffer without a
@@ -151,7 +151,7 @@ class AdamW(torch.optim.Optimizer):
         if self.capturable:
             dev_state = self._device_state(gi, group, dev, step - 1)
             check(lib.paradis_adamw_tick(dptr(dev_state), st), "adamw_tick")
-        check(lib.paradis_adamw_multi(dptr(c["ptrs"]), dptr(c["numel"]), dptr(c["chunk_tensor"]),
+        check(lib.paradis_adamw_multi_d(dptr(c["ptrs"]), dptr(c["numel"]), dptr(c["chunk_tensor"]),
                                       dptr(c["chunk_off"]), T, c["n_chunks"], group["lr"], b1, b2, group["eps"],
                                       group["weight_decay"], step, dptr(dev_state), st), "adamw_multi")
 
