@@ -424,6 +424,30 @@ int paradis_forecast_post(const float* output, int64_t out_bs, float* chunk, int
                           const float* p1, float eps_q, const int* units, int n_units, const double* plev,
                           int n_levels, const double* trig, int B, int C, int H, int W, void* stream);
 
+/* ---- validation scores (reference trainer.py:652-708, _get_report_rmse trainer.py:291-315, per-channel loss
+ * utils/loss.py:105-127).  One pass over pred and target [B, C, H, W] fp32 (batch strides pred_bs / target_bs in
+ * elements, dense states; neither is written) and a finishing kernel that combines the per-workgroup partials in
+ * double, in a fixed order (no atomics: bit-identical run to run), into the fp32 row out[1 + 2C + R]:
+ *   out[0]           mean_c(wf[c] * s[c] / N), s = sum wl[h] l(e) with wl, else sum l(e); e = pred - target; N = B*H*W
+ *   out[1 .. C]      wf[c] * s[c] / N                        out[1+C .. 2C]   sum l(e) / N   (unweighted)
+ *   out[1+2C+r]      sqrt(sum lat_w[h] d^2 / N) of channel rep_chan[r], d in physical units by rep_class[r]:
+ *                    1 z-score (target - pred) * p1, 2 specific humidity and 3 precipitation the difference of the two
+ *                    de-normalised values (codes, p0 = q_min, p1 = std | q_max as paradis_normalize_features;
+ *                    eps 1e-12 and shift 10 / eps 1e-6 as the reference's defaults)
+ * kind: 0 mse, 1 smooth reversed Huber (threshold delta) as paradis_loss_fwd_bwd, 2 none: out[0 .. 2C] are zeros and
+ * only report channels are read.  DEVICE tables: wf [C]; wl [H] or NULL; lat_w [H] (NULL allowed when R == 0);
+ * per channel rflag [C] (>= 0 a report channel, -1 none), rcls / rp0 / rp1 [C] (read where rflag >= 0); rchan [R].
+ * HOST arrays rep_chan / rep_class [R]: the same report list, checked here before anything is launched.
+ * workspace: paradis_val_score_ws_bytes(B, C, H, W) bytes.  B == 0 does nothing.
+ * W % 4 == 0 with 16-byte aligned planes takes 16-byte loads, anything else scalar loads: the same bits either way.
+ * Algorithmic HBM bytes: 8*B*C*H*W. */
+size_t paradis_val_score_ws_bytes(int B, int C, int H, int W);
+int paradis_val_score(const float* pred, int64_t pred_bs, const float* target, int64_t target_bs, const float* wf,
+                      const float* wl, const float* lat_w, int kind, float delta, const int* rep_chan,
+                      const int* rep_class, int R, const int* rflag, const int* rcls, const float* rp0,
+                      const float* rp1, const int* rchan, float* out, void* workspace, int B, int C, int H, int W,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
