@@ -448,6 +448,27 @@ int paradis_val_score(const float* pred, int64_t pred_bs, const float* target, i
                       const float* rp1, const int* rchan, float* out, void* workspace, int B, int C, int H, int W,
                       void* stream);
 
+/* ---- training diagnostics: per-group parameter / gradient / first-moment statistics (reference
+ * on_before_optimizer_step, trainer.py:844-923).  Two launches on `stream`, no host synchronisation, no atomics
+ * (bit-identical run to run).  Tables as paradis_adamw_multi_d: workgroup c reads at most paradis_param_stats_chunk()
+ * elements of tensor chunk_tensor[c] from element chunk_off[c]; ptrs [3][n_tensors] holds the fp32 parameter, gradient
+ * and first-moment addresses, a gradient or moment address of 0 means absent (a moment without a gradient is not read).
+ * The chunk table is sorted by group: the chunks of group g are group_first_chunk[g] .. group_first_chunk[g + 1] - 1
+ * (int32 [n_groups + 1], DEVICE; all other tables DEVICE too).  Sums are accumulated in double.
+ *   out [(n_groups + 1) * 8] fp32, row g = {sum p^2, sum g^2, sum g.m, sum m^2, grad norm sqrt(sum g^2),
+ *       gradratio = grad norm / pnorm, pnorm = max(sqrt(sum p^2), 1e-12),
+ *       alignment = sum g.m / (sqrt(sum g^2) sqrt(sum m^2) + 1e-12), 0 where sum m^2 = 0};
+ *   g.m and m^2 only over tensors with both a gradient and a moment; row n_groups: the same from the sums over all groups.
+ * workspace: paradis_param_stats_ws_bytes(n_chunks) bytes (four doubles per chunk), 8-byte aligned.
+ * n_chunks == 0 still writes out (zero sums, pnorm 1e-12); n_groups == 0 does nothing; at most 1024 groups.
+ * 16-byte loads where every present tensor's chunk start is 16-byte aligned, scalar loads otherwise: the same bits.
+ * Algorithmic HBM bytes: 12 per element with all three tensors present. */
+int paradis_param_stats_chunk(void);
+size_t paradis_param_stats_ws_bytes(int n_chunks);
+int paradis_param_stats(const int64_t* ptrs, const int64_t* numel, const int* chunk_tensor, const int64_t* chunk_off,
+                        const int* group_first_chunk, int n_tensors, int n_chunks, int n_groups, void* workspace,
+                        float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

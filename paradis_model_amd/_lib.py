@@ -111,6 +111,9 @@ SIGNATURES = {
     "paradis_forecast_post": (I, [P, L, P, L, L, P, L, L, P, P, P, F, P, I, P, I, P, I, I, I, I, P]),
     "paradis_val_score_ws_bytes": (S, [I, I, I, I]),
     "paradis_val_score": (I, [P, L, P, L, P, P, P, I, F, P, P, I, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "paradis_param_stats_chunk": (I, []),
+    "paradis_param_stats_ws_bytes": (S, [I]),
+    "paradis_param_stats": (I, [P, P, P, P, P, I, I, I, P, P, P]),
 }
 
 _missing = []

@@ -81,7 +81,7 @@ def next_input(model_input, output, num_common: int, n_inputs: int):
 
 def rollout_loss(model, loss_fn, batch, *, num_common: int, n_inputs: int, accum: int = 1,
                  detach_every: Optional[int] = None, keep_outputs: bool = False,
-                 backward: bool = True, amp: bool = False):
+                 backward: bool = True, amp: bool = False, on_step=None):
     """The autoregressive hot loop of ``training_step`` (reference trainer.py:508-576): per step
     assemble the input, run the model, accumulate ``loss/(S*accum)``, feed the prediction back;
     ``backward`` at chunk ends (every ``detach_every`` steps and at the last step), detaching the
@@ -89,7 +89,10 @@ def rollout_loss(model, loss_fn, batch, *, num_common: int, n_inputs: int, accum
 
     ``amp``: the forward and the loss of every step run under ``torch.autocast(bfloat16)``; the ``backward`` calls run
     OUTSIDE the autocast region, as under Lightning's ``precision="bf16-mixed"`` plugin (reference train.py:56) and
-    as the PyTorch AMP recipe prescribes."""
+    as the PyTorch AMP recipe prescribes.
+
+    ``on_step``: called with ``(out, true_data[:, step])`` after each step's loss (the per-channel training losses of
+    ``diagnostics.TrainStats``, reference trainer.py:544-556); it takes no part in the loss."""
     input_data, true_data, forcings, constant_data = batch
     constants = constant_data[:, :1].permute(0, 1, 4, 2, 3)
     forcings = forcings.permute(0, 1, 4, 2, 3)
@@ -104,6 +107,8 @@ def rollout_loss(model, loss_fn, batch, *, num_common: int, n_inputs: int, accum
             if keep_outputs:
                 outs.append(out.detach())
             chunk = chunk + loss_fn(out, true_data[:, step]) / (S * accum)
+            if on_step is not None:
+                on_step(out, true_data[:, step])
             input_data = next_input(mi, out, num_common, n_inputs).unsqueeze(1)
         if (detach_every is not None and (step + 1) % detach_every == 0) or step == S - 1:
             if backward:
@@ -116,11 +121,16 @@ def rollout_loss(model, loss_fn, batch, *, num_common: int, n_inputs: int, accum
 
 class TrainStep:
     """forward(S rollout steps) + ParadisLoss + backward + AdamW, the unit the benchmark times
-    (SURVEY.md section 8d).  AdamW hyper-parameters follow reference trainer.py:327-335."""
+    (SURVEY.md section 8d).  AdamW hyper-parameters follow reference trainer.py:327-335.
+
+    ``stats``: a ``diagnostics.TrainStats`` - the reference's ``log_additional_stats`` (trainer.py:520-556, 844-923): the
+    per-channel losses of every rollout step, the gradient statistics between the backward (DDP's all-reduces are
+    finished) and the optimiser step, and the step loss; read with ``stats.result()``.  ``None``: nothing is added."""
 
     def __init__(self, model, loss_fn, cfg, *, num_common: int = 83, n_inputs: int = 2, fused=None,
-                 capturable: bool = False, amp: bool = False):
+                 capturable: bool = False, amp: bool = False, stats=None):
         self.model, self.loss_fn = model, loss_fn
+        self.stats = stats
         # amp: forward and loss under torch.autocast(bfloat16) - the reference's shipped ``use_amp: true`` /
         # ``precision="bf16-mixed"`` (config/paradis_settings.yaml:75, train.py:56); parameters, gradients and the
         # optimiser stay fp32, as with Lightning's mixed-precision plugin
@@ -153,8 +163,17 @@ class TrainStep:
 
     def __call__(self, batch):
         self.opt.zero_grad(set_to_none=True)
-        loss, _ = rollout_loss(self.model, self.loss_fn, batch, num_common=self.num_common,
-                               n_inputs=self.n_inputs, detach_every=self.detach_every, amp=self.amp)
+        stats = self.stats
+        if stats is None:
+            loss, _ = rollout_loss(self.model, self.loss_fn, batch, num_common=self.num_common,
+                                   n_inputs=self.n_inputs, detach_every=self.detach_every, amp=self.amp)
+        else:
+            stats.begin_step()
+            loss, _ = rollout_loss(self.model, self.loss_fn, batch, num_common=self.num_common,
+                                   n_inputs=self.n_inputs, detach_every=self.detach_every, amp=self.amp,
+                                   on_step=stats.on_rollout_step)
+            stats.before_optimizer_step(self.opt)
+            stats.record_loss(loss)
         self.opt.step()
         return loss
 
@@ -216,6 +235,8 @@ class GraphedTrainStep:
         # the graph's optimiser nodes copy the pinned pointer tables of the capture on every replay: keep a snapshot
         # (and the captured gradient tensors, which live in the graph's private pool) for eager_step()
         self._tables = step.opt.snapshot_pointer_tables()
+        stats = getattr(step, "stats", None)      # the statistics launches were captured with the step: same for their table
+        self._stats_table = stats.snapshot_pointer_tables() if stats is not None else None
         self._captured_grads = [p.grad for g in step.opt.param_groups for p in g["params"]]
         # the capture ran the Python side of one step (host step counts advanced) without executing it on the
         # device: bring the device-side count of the captured tick back in line on first replay
@@ -249,10 +270,13 @@ class GraphedTrainStep:
         IT: an eager step issued right behind a replay would overwrite the table under a replay that has not got
         there yet (any GPU-bound configuration: ~150 ms of device time against ~30 ms of host enqueue), and that
         replay would apply AdamW with the eager step's gradient addresses.  So the host first waits for the last
-        replay to finish (ADVICE r4; ``tests/test_hip_graph.py::test_eager_step_right_behind_a_gpu_bound_replay``)."""
+        replay to finish (ADVICE r4; ``tests/test_hip_graph.py::test_eager_step_right_behind_a_gpu_bound_replay``).
+        The pinned address table of a ``TrainStep(stats=...)``'s statistics is snapshotted and restored the same way."""
         self._replayed.synchronize()
         loss = self.step(batch)
         self.step.opt.restore_pointer_tables(self._tables)
+        if self._stats_table is not None:
+            self.step.stats.restore_pointer_tables(self._stats_table)
         return loss
 
 
