@@ -59,6 +59,51 @@ def test_argument_validation_without_gpu():
     assert L.paradis_sl_advect_ws_bytes(2, 3, 8, 16, 0) >= 2 * 3 * 4 * 4
 
 
+# paradis_sl_advect_ws_bytes(B, K, H, W, flags) as the library of the commit before the advection unit was split
+# returned it (the layout did not change with the split: callers and saved workspaces depend on these totals)
+_S, _G, _TILED, _TILES = 4, 1, 2, 8      # PARADIS_ADVECT_SEPARABLE, _GENERIC, _TILED, _TILES (include/paradis_hip.h)
+_ADVECT_WS_BYTES = [
+    ((2, 3, 8, 16), 0, 768),                      # small plane, no flags
+    ((1, 4, 32, 64), _S, 768),                    # row64 plane
+    ((2, 4, 66, 72), _S, 768),                    # last size below the 64 KiB backward footprint: no strip region
+    ((2, 4, 68, 72), _S, 836864),                 # first size above it: strip region
+    ((2, 3, 64, 130), _S | _TILED, 1180928),      # ragged second strip
+    ((2, 4, 128, 256), _S, 3147008),              # large separable plane
+    ((2, 4, 128, 256), _S | _TILES, 768),         # tiles flag: no strip region
+    ((2, 4, 128, 256), _S | _G, 768),             # generic flag
+    ((2, 4, 128, 256), 0, 768),                   # non-separable: generic tiled
+    ((1, 2, 181, 360), _S, 1669376),              # tall grid
+    ((1, 1, 721, 1440), _S, 13290752),            # 0.25 degree grid
+]
+_ADVECT_WS_BYTES_DETERMINISTIC = [((2, 4, 128, 256), _S, 5244224), ((2, 4, 128, 256), 0, 2097984)]
+_WS_CHILD = """
+import json, sys
+from paradis_model_amd import _lib
+print(json.dumps([_lib.lib.paradis_sl_advect_ws_bytes(*shape, flags) for shape, flags in json.loads(sys.argv[1])]))
+"""
+
+
+def test_advect_workspace_sizes_are_pinned():
+    from paradis_model_amd import _lib, ops
+    assert (ops.ADVECT_SEPARABLE, ops.ADVECT_GENERIC, ops.ADVECT_TILED, ops.ADVECT_TILES) == (_S, _G, _TILED, _TILES)
+    import subprocess
+    import sys
+
+    def child(det, cases):      # (the switch is read once per process)
+        env = dict(os.environ, PARADIS_DETERMINISTIC=det)
+        r = subprocess.run([sys.executable, "-c", _WS_CHILD, json.dumps([[s, f] for s, f, _ in cases])], cwd=ROOT, env=env,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout.strip().splitlines()[-1]) == [n for _, _, n in cases], det
+
+    if os.environ.get("PARADIS_DETERMINISTIC", "")[:1] in ("", "0"):
+        for shape, flags, nbytes in _ADVECT_WS_BYTES:
+            assert _lib.lib.paradis_sl_advect_ws_bytes(*shape, flags) == nbytes, (shape, flags)
+    else:
+        child("0", _ADVECT_WS_BYTES)
+    child("1", _ADVECT_WS_BYTES_DETERMINISTIC)
+
+
 def test_ops_refuse_cpu_tensors():
     from paradis_model_amd import feed, ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):

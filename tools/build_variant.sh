@@ -3,6 +3,8 @@
 #   tools/build_variant.sh <name> "<source.hip ...>" "<extra hipcc flags>"        (runs without a GPU)
 # A macro that several units read takes all of them: SPLIT_SIGNED sits in gemm_common.h, so
 #   tools/build_variant.sh nosign "gemm.hip gemm_amp_fwd.hip gemm_amp_wgrad.hip" "-DSPLIT_SIGNED=0"
+# and the ADV_* knobs sit in advect_common.h, so an advection variant takes all four advect units:
+#   tools/build_variant.sh halo12 "advect.hip advect_planes.hip advect_tilerow.hip advect_strips.hip" "-DADV_HALO_BWD=12"
 # A/B the variants on one box with PARADIS_HIP_LIB=build/variants/lib_<name>.so (tools/adv_trace*.sh, tools/ab_libs.sh).
 set -e
 NAME=$1; SRCS=$2; FLAGS=$3
@@ -12,8 +14,7 @@ OBJS=$(ls $R/build/obj/*.o)
 for SRC in $SRCS; do
   BASE=$(basename $SRC .hip)
   EXTRA="-fno-slp-vectorize"
-  [ $BASE = advect ] && EXTRA="$EXTRA -ffp-contract=off"
-  [ $BASE = feed ] && EXTRA="$EXTRA -ffp-contract=off"
+  case $BASE in advect*|feed) EXTRA="$EXTRA -ffp-contract=off";; esac
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -munsafe-fp-atomics $EXTRA $FLAGS \
       -c $R/paradis_model_amd/csrc/$BASE.hip -o $OUT/${BASE}_$NAME.o
   OBJS="$(echo "$OBJS" | grep -v "/$BASE.o") $OUT/${BASE}_$NAME.o"
