@@ -578,7 +578,7 @@ def _dwconv_geo_bwd(gy, x, weight, addend, has_bias):
     """(gx (+ addend), gw, gb) of the stencil in one call: with k = 5 on the reference grids one kernel that reads gy
     once (paradis_dwconv_geo_bwd); bit-identical to ``dwconv_geo_dgrad`` (``_add``) + ``dwconv_geo_wgrad``."""
     _f32(x, weight, addend)
-    _f32_or_bf16(gy)
+    _f32_or_bf16(GEMM_BF16, gy)
     B, C, H, W = x.shape
     k = weight.shape[-1]
     if _is16(gy) and not lib.paradis_dwconv_geo_bwd16_ok(H, W, k):
@@ -828,7 +828,7 @@ def _channel_norm_backward(gy, x1, x2, weight, mean, rstd, add):
     """``add``: a gradient that reaches x1 along another path (the residual branch around the block);
     it is added inside the kernel instead of by a separate accumulation pass."""
     _f32(x1, x2, add)
-    _f32_or_bf16(gy)
+    _f32_or_bf16(GEMM_BF16, gy)
     x1, bs1 = _plane_view(x1)
     B, C1, H, W = x1.shape
     C2, bs2 = 0, 0

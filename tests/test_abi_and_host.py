@@ -104,6 +104,29 @@ def test_advect_workspace_sizes_are_pinned():
     child("1", _ADVECT_WS_BYTES_DETERMINISTIC)
 
 
+# (B, C, H, W, k) -> paradis_dwconv_geo_bwd16_ok(H, W, k), paradis_dwconv_geo_wgrad_ws_bytes(B, C, H, W, k) as the library
+# of the commit before stencil.hip was split by schedule returned them (both are host-only functions)
+_DWCONV_HOST = [
+    ((2, 6, 32, 64, 5), 1, 1504),             # whole plane
+    ((2, 6, 31, 64, 5), 1, 1504),             # a shorter one
+    ((2, 6, 33, 64, 5), 0, 2752),             # one row too tall: two tiles
+    ((2, 6, 32, 64, 3), 0, 736),              # k = 3: the generic kernels
+    ((2, 6, 32, 68, 5), 0, 2752),             # ragged second tile column
+    ((1, 3, 70, 130, 5), 0, 3064),            # rows that are not whole float4
+    ((3, 1030, 32, 64, 5), 1, 321616),        # many channels: two chunks on one path, three on the other
+    ((2, 2100, 40, 72, 5), 0, 873856),        # more channels than workgroups asked for
+    ((0, 4, 64, 128, 5), 0, 672),             # empty batch
+    ((1, 2, 721, 1440, 5), 0, 110288),        # 0.25 degree grid
+]
+
+
+def test_dwconv_workspace_sizes_and_bf16_cotangent_grids_are_pinned():
+    from paradis_model_amd import _lib
+    for (B, C, H, W, k), ok16, nbytes in _DWCONV_HOST:
+        assert _lib.lib.paradis_dwconv_geo_bwd16_ok(H, W, k) == ok16, (H, W, k)
+        assert _lib.lib.paradis_dwconv_geo_wgrad_ws_bytes(B, C, H, W, k) == nbytes, (B, C, H, W, k)
+
+
 def test_ops_refuse_cpu_tensors():
     from paradis_model_amd import feed, ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -43,6 +43,19 @@ def test_cpu_tensors_are_rejected_loudly():
         torch.ops.paradis.add(x, x)
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float64])
+def test_backward_ops_refuse_cotangents_that_are_neither_fp32_nor_bf16(dtype):
+    """an fp16 / fp64 cotangent must not reach the fp32 kernels as raw bytes.  ``ops._dwconv_geo_bwd`` and
+    ``ops._channel_norm_backward`` name the registered ops, which the dispatcher refuses for CPU tensors before any code
+    of ours runs; ``ops.RAW`` holds the Python functions behind them, whose dtype check precedes any device call."""
+    assert ops._dwconv_geo_bwd is ops.OPS["dwconv_geo_bwd"] and ops._channel_norm_backward is ops.OPS["channel_norm_backward"]
+    gy, x = torch.randn(1, 2, 8, 16).to(dtype), torch.randn(1, 2, 8, 16)
+    with pytest.raises(RuntimeError, match="ops are fp32"):
+        ops.RAW["dwconv_geo_bwd"](gy, x, torch.randn(2, 1, 5, 5), None, False)
+    with pytest.raises(RuntimeError, match="ops are fp32"):
+        ops.RAW["channel_norm_backward"](gy, x, None, torch.ones(2), torch.zeros(1, 1, 8, 16), torch.ones(1, 1, 8, 16), None)
+
+
 def _fake_model(mode, cfg, H, W):
     from paradis_model_amd.model import Paradis
     _, lg, og = make_grid(H, W, False)

@@ -242,6 +242,34 @@ def test_dwconv_geo_bwd_one_pass_is_bit_identical_to_the_two_calls(ops, B, C, H,
     assert gb.numel() == (C if bias else 0)
 
 
+def _one_float_in(t):
+    """a contiguous copy of ``t`` that starts one float into its buffer: 4-byte aligned, not 16"""
+    v = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)[1:1 + t.numel()].view(t.shape)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v.copy_(t)
+
+
+@pytest.mark.parametrize("B,C,H,W,k", [(2, 6, 32, 64, 5), (2, 3, 64, 128, 5), (2, 3, 32, 68, 5)])   # whole planes, tiles, ragged tiles
+@pytest.mark.parametrize("which", ["gy", "x", "addend", "all", "gy and x, no addend"])
+def test_dwconv_geo_on_misaligned_views_equals_the_two_calls_and_the_aligned_result(ops, B, C, H, W, k, which):
+    """The allocator hands out 512-byte aligned tensors, so the alignment half of the schedule choice is reached only by
+    views: gy, x or the addend 4-byte aligned only, one at a time and together.  paradis_dwconv_geo_bwd still has the
+    bits of dgrad(_add) + wgrad on the same views (both sides choose by the same rule), and the values are those of the
+    aligned call; likewise forward."""
+    gy, x, w = seeded(1, B, C, H, W).cuda(), seeded(2, B, C, H, W).cuda(), seeded(3, C, 1, k, k, scale=1.0 / k).cuda()
+    ad, b = None if "no addend" in which else seeded(4, B, C, H, W).cuda(), seeded(5, C).cuda()
+    gym, xm, adm = (_one_float_in(t) if t is not None and (name in which or which == "all") else t
+                    for name, t in (("gy", gy), ("x", x), ("addend", ad)))
+    gx, gw, gb = ops._dwconv_geo_bwd(gym, xm, w, adm, True)
+    gx2 = ops._dwconv_geo_dgrad(gym, w) if adm is None else ops._dwconv_geo_dgrad_add(gym, w, adm)
+    gw2, gb2 = ops._dwconv_geo_wgrad(gym, xm, k, True)
+    assert torch.equal(gx, gx2) and torch.equal(gw, gw2) and torch.equal(gb, gb2)
+    for what, got, want in zip(("gx", "gw", "gb"), (gx, gw, gb), ops._dwconv_geo_bwd(gy, x, w, ad, True)):
+        _cmp(got, want.cpu(), BWD, what)
+    if xm is not x:
+        _cmp(ops._dwconv_geo(xm, w, b), ops._dwconv_geo(x, w, b).cpu(), FWD, "y")
+
+
 def test_sepconv_golden(ops):
     g = load_golden("g3_blocks.pt")
     for k in (5, 7):

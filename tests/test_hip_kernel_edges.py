@@ -1,5 +1,5 @@
 """The small streaming / reduction kernels against plain fp64 references (tests/_refs64.py) at every dispatch edge:
-the shapes, alignments and sizes at which csrc/stencil.hip, misc.hip, norm.hip and train.hip pick another kernel,
+the shapes, alignments and sizes at which csrc/resample.hip, misc.hip, norm.hip and train.hip pick another kernel,
 another chunk count or another tail loop.  The parameter lists are derived from the dispatch conditions in the source;
 the comment next to a case names the branch it selects.
 
@@ -117,7 +117,7 @@ def _leaf32(t):
 
 
 # ================================================================================================ avgpool
-# stencil.hip: one thread per output (forward) / per input cell (backward, a gather over the windows [o s, o s + 4] of
+# resample.hip: one thread per output (forward) / per input cell (backward, a gather over the windows [o s, o s + 4] of
 # the padded plane that hold an alias of the cell); grid-stride loop above 8192 workgroups (721x1440: 4056 - below);
 # strides 5: windows abut; 7: they leave rows / columns uncovered; 3, 5, 7 do not divide H - 1 or W of most grids.
 POOL_GRIDS = [(12, 16), (13, 16),

@@ -5,6 +5,8 @@
 #   tools/build_variant.sh nosign "gemm.hip gemm_amp_fwd.hip gemm_amp_wgrad.hip" "-DSPLIT_SIGNED=0"
 # and the ADV_* knobs sit in advect_common.h, so an advection variant takes all four advect units:
 #   tools/build_variant.sh halo12 "advect.hip advect_planes.hip advect_tilerow.hip advect_strips.hip" "-DADV_HALO_BWD=12"
+# Likewise the DWCONV_* knobs sit in stencil_common.h, so a stencil variant takes all three stencil units:
+#   tools/build_variant.sh notiles "stencil.hip stencil_planes.hip stencil_generic.hip" "-DDWCONV_TILES=0"
 # A/B the variants on one box with PARADIS_HIP_LIB=build/variants/lib_<name>.so (tools/adv_trace*.sh, tools/ab_libs.sh).
 set -e
 NAME=$1; SRCS=$2; FLAGS=$3
