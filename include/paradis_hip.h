@@ -352,6 +352,12 @@ int paradis_adamw_step_d(float* p, const float* g, float* m, float* v, int64_t n
 int paradis_adamw_multi_d(const int64_t* ptrs, const int64_t* numel, const int* chunk_tensor,
                           const int64_t* chunk_off, int n_tensors, int n_chunks, double lr, double beta1,
                           double beta2, double eps, double weight_decay, int step, const int* dev_state, void* stream);
+/* Learning-rate schedule on the device, one launch of one wavefront per optimiser step, behind the groups' ticks:
+ * states = DEVICE table of n_groups addresses (int64; 0 = skip the group) of the int32[2] states above, table = DEVICE
+ * fp32 [n_groups][n_steps].  With s = the group's already-ticked, 1-based step count:
+ * state_g[1] = bits(table[g][min(s - 1, n_steps - 1)]) - past the end of the table its last entry holds.  A plain kernel
+ * on `stream` (no host synchronisation, no copy or fill node): a captured training step walks the schedule by itself. */
+int paradis_lr_schedule(const int64_t* states, const float* table, int n_groups, int n_steps, void* stream);
 
 /* ---- f1 (AMSE): the spectral loss of reference utils/amse_loss.py on the equiangular grid H x W, W = 2(H-1), poles
  * included; row j of a plane is colatitude pi*j/(H-1) (RealSHT's order).  M = H-1 degrees / orders are used.
@@ -380,6 +386,17 @@ int paradis_muon_step(const int64_t* ptrs, int table_stride, int T, int rows, in
                       float lr_adj, float mu, float beta2, float weight_decay, float eps, int nesterov,
                       int normuon, int split /* Newton-Schulz products on the bf16-split GEMM */,
                       void* workspace, void* stream);
+/* The same step with the learning rate on the device.  dev_state (NULL = exactly paradis_muon_step, `lr_scale` unused):
+ * the int32[2] state of paradis_adamw_multi_d, [1] = the bits of the fp32 learning rate.  The one kernel of the step
+ * that uses the learning rate then reads lr = dev_state[1] and forms 1 - lr*weight_decay (fp32) and
+ * lr_adj = (float)((double)lr * lr_scale) itself; `lr` and `lr_adj` are ignored, and nothing about the learning rate is
+ * a launch constant (harness.GraphedTrainStep).  lr_scale: the shape factor of the adjusted learning rate - 1,
+ * sqrt(fan_out / fan_in) or 0.2 sqrt(max(fan_out, fan_in)).  Agrees with the host-scalar entry to 1 ulp of the two
+ * coefficients. */
+int paradis_muon_step_d(const int64_t* ptrs, int table_stride, int T, int rows, int cols, float lr,
+                        float lr_adj, float mu, float beta2, float weight_decay, float eps, int nesterov,
+                        int normuon, int split, void* workspace, const int* dev_state, double lr_scale,
+                        void* stream);
 /* Plain batched GEMM C_b[M,N] = A_b[M,K] B_b[K,N] (row-major; AT = optional [K,M] transposes of A_b,
  * enabling the LDS-DMA kernel; split_ws = optional nbatch * paradis_pw_gemm_split_bytes(M,K,PARADIS_GEMM_BF16X3) bytes of
  * scratch selecting the bf16-split arithmetic) used by the Newton-Schulz iteration. */

@@ -97,12 +97,14 @@ SIGNATURES = {
     "paradis_adamw_step": (I, [P, P, P, P, L, F, F, F, F, F, I, P]),
     "paradis_muon_ws_bytes": (S, [I, I, I]),
     "paradis_muon_step": (I, [P, I, I, I, I, F, F, F, F, F, F, I, I, I, P, P]),
+    "paradis_muon_step_d": (I, [P, I, I, I, I, F, F, F, F, F, F, I, I, I, P, P, D, P]),
     "paradis_bgemm": (I, [P, P, P, P, I, I, I, I, L, L, L, L, P, P]),
     "paradis_adamw_chunk": (I, []),
     "paradis_adamw_multi": (I, [P, P, P, P, I, I, F, F, F, F, F, I, P, P]),
     "paradis_adamw_tick": (I, [P, P]),
     "paradis_adamw_step_d": (I, [P, P, P, P, L, D, D, D, D, D, I, P]),
     "paradis_adamw_multi_d": (I, [P, P, P, P, I, I, D, D, D, D, D, I, P, P]),
+    "paradis_lr_schedule": (I, [P, P, I, I, P]),
     "paradis_amse_table_floats": (S, [I]),
     "paradis_amse_tables_ws_bytes": (S, [I]),
     "paradis_amse_tables": (I, [P, P, P, I, I, P]),

@@ -131,11 +131,24 @@ normuon_rows_kernel(float* __restrict__ X, Tab tab, int rows, int cols, int64_t 
 }
 
 // w_t = w_t (1 - lr wd) - alpha ratio_t u_t,  ratio = sqrt(sums[2t]) / max(sqrt(sums[2t+1]), 1e-8) when
-// sums given; u is read with strides (it may be held transposed)
+// sums given; u is read with strides (it may be held transposed).
+// dev (optional): {int32 step, bits of the fp32 lr} of the group on the device (the layout of adamw_multi_kernel): the
+// two coefficients that depend on the learning rate are then formed here, so that a HIP graph captured around the step
+// holds no learning rate in its kernel arguments.  decay = 1 - lr wd in fp32 with the product rounded on its own (what
+// the host path's `1.0f - lr * weight_decay` does on a host without contraction), alpha = lr * lr_scale in double rounded once (the host path rounds
+// Python's double product): the two paths agree to 1 ulp of the coefficients.
 __global__ void __launch_bounds__(256)
 muon_apply_kernel(Tab tab, const float* __restrict__ U, int rows, int cols, int64_t urs, int64_t ucs,
-                  float decay, float alpha, const float* __restrict__ sums) {
+                  float decay, float alpha, const float* __restrict__ sums, const int* __restrict__ dev, float wd,
+                  double lr_scale) {
   const int t = blockIdx.y;
+  if (dev) {     // (uniform over the grid)
+#pragma clang fp contract(off)     // lr * wd rounded on its own, as the host forms it: no fma(-lr, wd, 1)
+    const float lr = __int_as_float(dev[1]);
+    const float lr_wd = lr * wd;
+    decay = 1.0f - lr_wd;
+    alpha = (float)((double)lr * lr_scale);
+  }
   float ratio = 1.0f;
   if (sums) ratio = sqrtf(sums[2 * t]) / fmaxf(sqrtf(sums[2 * t + 1]), 1e-8f);
   const float k = alpha * ratio;
@@ -167,9 +180,13 @@ extern "C" size_t paradis_muon_ws_bytes(int T, int rows, int cols) {
 // (conv weights flattened to [out, in*kh*kw] by the caller).  ptrs: DEVICE table [4][table_stride] of
 // the addresses of w, g, m (momentum, [rows*cols]) and v (NorMuon per-row state [rows]; unused for
 // Muon), this group's entries first.  lr_adj = the shape-adjusted learning rate.
-extern "C" int paradis_muon_step(const int64_t* ptrs, int table_stride, int T, int rows, int cols, float lr,
-                                 float lr_adj, float mu, float beta2, float weight_decay, float eps,
-                                 int nesterov, int normuon, int split, void* workspace, void* stream) {
+// dev_state (optional, NULL = use `lr` and `lr_adj`): int32[2] on the device, [1] = the bits of the fp32 learning rate
+// (the state of paradis_adamw_multi_d); the update then uses lr = dev_state[1] and lr_adj = lr * lr_scale, formed on
+// the device by the one kernel of the step that needs them (muon_apply_kernel).
+extern "C" int paradis_muon_step_d(const int64_t* ptrs, int table_stride, int T, int rows, int cols, float lr,
+                                   float lr_adj, float mu, float beta2, float weight_decay, float eps,
+                                   int nesterov, int normuon, int split, void* workspace, const int* dev_state,
+                                   double lr_scale, void* stream) {
   PD_REQUIRE(T >= 0 && rows >= 1 && cols >= 1 && table_stride >= T, "muon_step: bad shape");
   if (T == 0) return 0;
   PD_REQUIRE(ptrs != nullptr && workspace != nullptr, "muon_step: table / workspace required");
@@ -230,7 +247,15 @@ extern "C" int paradis_muon_step(const int64_t* ptrs, int table_stride, int T, i
     hipLaunchKernelGGL(normuon_rows_kernel, dim3(rows, T), dim3(256), 0, st, cur, tab, rows, cols, urs, ucs, beta2,
                        sc + T);
   hipLaunchKernelGGL(muon_apply_kernel, gn, dim3(256), 0, st, tab, (const float*)cur, rows, cols, urs, ucs,
-                     1.0f - lr * weight_decay, lr_adj, normuon ? (const float*)(sc + T) : (const float*)nullptr);
+                     1.0f - lr * weight_decay, lr_adj, normuon ? (const float*)(sc + T) : (const float*)nullptr, dev_state,
+                     weight_decay, lr_scale);
   PD_CHECK_LAUNCH("muon_step");
   return 0;
+}
+
+extern "C" int paradis_muon_step(const int64_t* ptrs, int table_stride, int T, int rows, int cols, float lr,
+                                 float lr_adj, float mu, float beta2, float weight_decay, float eps,
+                                 int nesterov, int normuon, int split, void* workspace, void* stream) {
+  return paradis_muon_step_d(ptrs, table_stride, T, rows, cols, lr, lr_adj, mu, beta2, weight_decay, eps, nesterov,
+                             normuon, split, workspace, nullptr, 1.0, stream);
 }

@@ -160,6 +160,18 @@ adamw_multi_kernel(const int64_t* __restrict__ ptrs /* [4][T]: p, g, m, v */, co
 
 __global__ void adamw_tick_kernel(int* __restrict__ dev) { dev[0] += 1; }
 
+// thread g: the learning rate of group g for its (already ticked, 1-based) step count, out of row g of the table;
+// past the end of the table the last entry holds.  An address of 0 = a group without a device state.
+__global__ void __launch_bounds__(64)
+lr_schedule_kernel(const int64_t* __restrict__ states, const float* __restrict__ table, int G, int n) {
+  for (int g = threadIdx.x; g < G; g += 64) {
+    int* st = reinterpret_cast<int*>(states[g]);
+    if (st == nullptr) continue;
+    const int k = min(max(st[0] - 1, 0), n - 1);
+    st[1] = __float_as_int(table[(int64_t)g * n + k]);
+  }
+}
+
 inline int blocks_for(int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 8));
 }
@@ -232,6 +244,17 @@ extern "C" int paradis_adamw_tick(int* dev_state, void* stream) {
   PD_REQUIRE(dev_state != nullptr, "adamw_tick: state missing");
   hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, dev_state);
   PD_CHECK_LAUNCH("adamw_tick");
+  return 0;
+}
+
+// states[g] (DEVICE table of n_groups addresses, 0 = skip) -> int32[2] state of group g; table [n_groups][n_steps] fp32
+// on the device: state_g[1] = bits(table[g][min(state_g[0] - 1, n_steps - 1)]).  One launch of one wavefront.
+extern "C" int paradis_lr_schedule(const int64_t* states, const float* table, int n_groups, int n_steps, void* stream) {
+  PD_REQUIRE(n_groups >= 0 && n_steps >= 1, "lr_schedule: bad arguments");
+  if (n_groups == 0) return 0;
+  PD_REQUIRE(states != nullptr && table != nullptr, "lr_schedule: tables missing");
+  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, states, table, n_groups, n_steps);
+  PD_CHECK_LAUNCH("lr_schedule");
   return 0;
 }
 

@@ -125,10 +125,16 @@ class TrainStep:
 
     ``stats``: a ``diagnostics.TrainStats`` - the reference's ``log_additional_stats`` (trainer.py:520-556, 844-923): the
     per-channel losses of every rollout step, the gradient statistics between the backward (DDP's all-reduces are
-    finished) and the optimiser step, and the step loss; read with ``stats.result()``.  ``None``: nothing is added."""
+    finished) and the optimiser step, and the step loss; read with ``stats.result()``.  ``None``: nothing is added.
+
+    ``schedule``: a ``(lr_lambda, total_steps)`` pair or what ``schedule.from_config`` returns - the reference's
+    ``LambdaLR`` with interval ``"step"`` (trainer.py:416-456), tabulated once (``schedule.DeviceSchedule``).  A capturable
+    optimiser reads the table on the device, one launch inside ``opt.step()`` (so inside a captured graph); any other
+    optimiser gets ``group["lr"]`` set from the same table before every ``opt.step()``.  ``None``: the learning rate is
+    whatever ``group["lr"]`` holds."""
 
     def __init__(self, model, loss_fn, cfg, *, num_common: int = 83, n_inputs: int = 2, fused=None,
-                 capturable: bool = False, amp: bool = False, stats=None):
+                 capturable: bool = False, amp: bool = False, stats=None, schedule=None):
         self.model, self.loss_fn = model, loss_fn
         self.stats = stats
         # amp: forward and loss under torch.autocast(bfloat16) - the reference's shipped ``use_amp: true`` /
@@ -151,7 +157,7 @@ class TrainStep:
             if cls is None:
                 raise ValueError(f"Optimizer {name} not supported. Choose between normuon|muon")
             self.opt = cls(groups, lr=o.lr, weight_decay=o.weight_decay, betas=(o.beta1, o.beta2),
-                           use_triton=True)
+                           use_triton=True, capturable=capturable)
         elif on_hip and fused is None:
             from .optim import AdamW   # HIP kernel, torch.optim.AdamW semantics
             self.opt = AdamW(params, lr=o.lr, weight_decay=o.weight_decay, betas=(o.beta1, o.beta2),
@@ -160,6 +166,16 @@ class TrainStep:
             self.opt = torch.optim.AdamW(params, lr=o.lr, weight_decay=o.weight_decay,
                                          betas=(o.beta1, o.beta2), fused=bool(fused))
         self.detach_every = o.get("detach_gradient_every", None)
+        self.schedule = None          # the host-driven table (non-capturable optimiser); a capturable one owns its own
+        self.opt_steps = 0            # optimiser steps taken through this object
+        if schedule is not None:
+            from .schedule import DeviceSchedule, as_schedule
+            sch = as_schedule(schedule)
+            table = DeviceSchedule(self.opt, sch.lr_lambda, sch.total_steps)
+            if getattr(self.opt, "capturable", False):
+                self.opt.attach_schedule(table)
+            else:
+                self.schedule = table
 
     def __call__(self, batch):
         self.opt.zero_grad(set_to_none=True)
@@ -174,18 +190,25 @@ class TrainStep:
                                    on_step=stats.on_rollout_step)
             stats.before_optimizer_step(self.opt)
             stats.record_loss(loss)
+        if self.schedule is not None:
+            for gi, group in enumerate(self.opt.param_groups):
+                group["lr"] = self.schedule.host_lr(gi, self.opt_steps)
         self.opt.step()
+        self.opt_steps += 1
         return loss
 
 
 class GraphedTrainStep:
-    """The whole training step - forward (S rollout steps), ParadisLoss, backward, AdamW: ~2,500 kernel launches -
+    """The whole training step - forward (S rollout steps), ParadisLoss, backward, optimiser (AdamW, Muon or NorMuon, with
+    or without a device-side learning-rate schedule): ~2,500 kernel launches -
     captured once into a HIP graph (``torch.cuda.CUDAGraph``) and replayed: the host enqueues one graph launch per
     step instead of walking dispatcher -> autograd -> Python kernel -> ctypes for every op (23.5 ms of host time per
     step at 32x64, the bound below ~4 samples per GPU).  Everything on the path is capture-safe: the ops launch on
     the current stream through the C ABI without host synchronisation, workspaces come from the caching allocator
     (the graph's private pool under capture), and the optimiser's step count and learning rate live on the device
-    (``optim.AdamW(capturable=True)``).
+    (``optim.AdamW(capturable=True)``, and the same flag of ``optim.Muon`` / ``optim.NorMuon``).  A schedule given to the
+    ``TrainStep`` is a launch inside the optimiser step that reads the DEVICE step count, so the replayed learning rates
+    are those of an eager run: the capture advances only host counters, and the first replay does not advance them again.
 
     ``step`` must be a ``TrainStep(..., capturable=True)``; ``example_batch`` fixes the shapes.  ``warmup`` eager
     steps run first on a side stream (they are real optimiser steps: kernel attributes, optimiser state and the

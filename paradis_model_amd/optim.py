@@ -14,14 +14,29 @@ class AdamW(torch.optim.Optimizer):
     """``capturable=True``: the step count and the learning rate of every group also live on the device
     (``paradis_adamw_multi_d(..., dev_state)``), so a HIP graph captured around ``step()`` stays valid from replay to
     replay (``harness.GraphedTrainStep``); same formula, the bias corrections formed in double on the device (agrees with the
-    host-side path to ~1 ulp of the fp32 corrections: the device pow is not the host libm, test bound 1e-6)."""
+    host-side path to ~1 ulp of the fp32 corrections: the device pow is not the host libm, test bound 1e-6).
+
+    The learning rate of a capturable optimiser changes in one of two ways: the host sets ``group["lr"]`` and calls
+    ``sync_device_state()`` (a blocking copy: fine per epoch, a queue drain when done per step), or a
+    ``schedule.DeviceSchedule`` is attached (``attach_schedule``) and one launch inside ``step()`` - behind the ticks of the
+    groups' step counts, in front of their updates - writes every group's learning rate for its step from a device table;
+    ``group["lr"]`` then mirrors the table."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False):
         if lr < 0 or eps < 0 or weight_decay < 0 or not 0 <= betas[0] < 1 or not 0 <= betas[1] < 1:
             raise ValueError("invalid AdamW hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.capturable = bool(capturable)
-        self._dev_state = {}      # group index -> (int32[2] device tensor, lr it holds)
+        # keyed, like the pointer-table caches, by the group's index in the FULL ``param_groups`` (a subclass that
+        # updates only some groups by this class's kernels must not renumber them: sync_device_state walks the full list)
+        self._dev_state = {}      # group index -> [int32[2] device tensor, lr it holds]
+        self._schedule = None
+
+    def attach_schedule(self, schedule) -> None:
+        """``schedule``: a ``schedule.DeviceSchedule`` built on this optimiser (``None`` detaches)"""
+        if schedule is not None and not self.capturable:
+            raise ValueError("a device schedule needs a capturable optimiser (the learning rate must live on the device)")
+        self._schedule = schedule
 
     def _device_state(self, gi, group, dev, step_before):
         """int32[2] = [step count, bits of lr] of group ``gi`` on the device (created at the group's first update)"""
@@ -32,7 +47,10 @@ class AdamW(torch.optim.Optimizer):
             ent = [torch.tensor([step_before, lr_bits], dtype=torch.int32, device=dev), float(group["lr"])]
             self._dev_state[gi] = ent
         elif ent[1] != float(group["lr"]):
-            if torch.cuda.is_current_stream_capturing():
+            if self._schedule is not None:
+                ent[1] = float(group["lr"])      # the schedule launch writes it on the device
+                return ent[0]
+            if ent[0].is_cuda and torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("AdamW(capturable): the learning rate changed inside a graph capture")
             ent[0][1:2].copy_(torch.tensor([lr_bits], dtype=torch.int32), non_blocking=False)
             ent[1] = float(group["lr"])
@@ -44,13 +62,31 @@ class AdamW(torch.optim.Optimizer):
             if gi in self._dev_state:
                 self._device_state(gi, group, self._dev_state[gi][0].device, 0)
 
+    def _group_step(self, group):
+        """the step count of the group's parameters that have state (``None``: none has)"""
+        for p in group["params"]:
+            st = self.state.get(p)
+            if st:
+                return int(st["step"])
+        return None
+
     def note_replayed(self):
-        """a captured step() was replayed: advance the host-side step counts (state_dict compatibility)"""
-        for group in self.param_groups:
+        """a captured step() was replayed: advance the host-side step counts (state_dict compatibility) and, under a
+        device schedule, set ``group["lr"]`` to what the replay used"""
+        for gi, group in enumerate(self.param_groups):
             for p in group["params"]:
                 st = self.state.get(p)
                 if st:
                     st["step"] += 1
+            if self._schedule is not None:
+                self._mirror_lr(gi, group, self._group_step(group))
+
+    def _mirror_lr(self, gi, group, step):
+        if step is not None and step >= 1:
+            lr = self._schedule.host_lr(gi, step - 1)
+            group["lr"] = lr
+            if gi in self._dev_state:
+                self._dev_state[gi][1] = lr
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -58,52 +94,82 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        st = stream_ptr()
-        for gi, group in enumerate(self.param_groups):
-            b1, b2 = group["betas"]
-            params = [p for p in group["params"] if p.grad is not None]
-            if not params:
-                continue
-            steps = set()
-            for p in params:
-                require_hip(p, p.grad)
-                state = self.state[p]
-                if not state:
-                    state["step"] = 0
-                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                state["step"] += 1
-                steps.add(int(state["step"]))
-            uniform = len(steps) == 1 and all(p.is_contiguous() and p.grad.is_contiguous() for p in params)
-            if uniform and (len(params) > 1 or self.capturable):
-                self._step_group_fused(gi, group, params, steps.pop(), st)
-                continue
-            if self.capturable:
-                raise RuntimeError("AdamW(capturable) needs contiguous parameters with one common step count per group")
-            for p in params:
-                state = self.state[p]
-                g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                check(lib.paradis_adamw_step_d(dptr(p), dptr(g), dptr(state["exp_avg"]),
-                                             dptr(state["exp_avg_sq"]), p.numel(), group["lr"], b1, b2,
-                                             group["eps"], group["weight_decay"], int(state["step"]), st),
-                      "adamw_step")
-        ops.weights_updated()     # the kernels write through raw pointers: no version-counter bump
+        plans = [pl for pl in (self._prepare_group(gi, g) for gi, g in enumerate(self.param_groups)) if pl is not None]
+        self._run(plans)
         return loss
 
+    def _run(self, plans):
+        """``plans``: what ``_prepare_group`` returned for the groups that have gradients.  Capturable: first every
+        group's device step count is advanced and (with a schedule) its learning rate written, then the updates run."""
+        if self.capturable:
+            for pl in plans:
+                gi, group = pl["gi"], pl["group"]
+                if pl["step"] is None:
+                    raise RuntimeError("AdamW(capturable) needs contiguous parameters with one common step count per group")
+                if self._schedule is not None:
+                    self._mirror_lr(gi, group, pl["step"])
+                pl["dev_state"] = self._device_state(gi, group, pl["params"][0].device, pl["step"] - 1)
+                check(lib.paradis_adamw_tick(dptr(pl["dev_state"]), stream_ptr()), "adamw_tick")
+            if self._schedule is not None and plans:
+                self._schedule.apply()
+        for pl in plans:
+            self._update_group(pl)
+        ops.weights_updated()     # the kernels write through raw pointers: no version-counter bump
+
+    def _prepare_group(self, gi, group):
+        """host bookkeeping of one group's update: state creation, step counts.  ``step``: the common step count when
+        the group can go through the fused launch, else ``None``."""
+        params = [p for p in group["params"] if p.grad is not None]
+        if not params:
+            return None
+        steps = set()
+        for p in params:
+            require_hip(p, p.grad)
+            state = self.state[p]
+            if not state:
+                state["step"] = 0
+                state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state["step"] += 1
+            steps.add(int(state["step"]))
+        uniform = len(steps) == 1 and all(p.is_contiguous() and p.grad.is_contiguous() for p in params)
+        return dict(gi=gi, group=group, params=params, step=steps.pop() if uniform else None, dev_state=None)
+
+    def _update_group(self, pl):
+        group, params = pl["group"], pl["params"]
+        st = stream_ptr()
+        if pl["step"] is not None and (len(params) > 1 or self.capturable):
+            self._step_group_fused(pl["gi"], group, params, pl["step"], st, pl["dev_state"])
+            return
+        b1, b2 = group["betas"]
+        for p in params:
+            state = self.state[p]
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            check(lib.paradis_adamw_step_d(dptr(p), dptr(g), dptr(state["exp_avg"]),
+                                         dptr(state["exp_avg_sq"]), p.numel(), group["lr"], b1, b2,
+                                         group["eps"], group["weight_decay"], int(state["step"]), st),
+                  "adamw_step")
+
+    def _pointer_caches(self):
+        for name in ("_fused_cache", "_muon_cache"):
+            for gi, c in self.__dict__.get(name, {}).items():
+                yield (name, gi), c
+
     def snapshot_pointer_tables(self):
-        """copies of the pinned address tables of the fused groups (``harness.GraphedTrainStep``: a captured step
-        re-reads them on every replay)"""
-        return {gi: c["host"].clone() for gi, c in self.__dict__.get("_fused_cache", {}).items()}
+        """copies of the pinned address tables of the fused groups and of the Muon-family matrix groups
+        (``harness.GraphedTrainStep``: a captured step re-reads them on every replay)"""
+        return {key: c["host"].clone() for key, c in self._pointer_caches()}
 
     def restore_pointer_tables(self, tables) -> None:
-        for gi, t in tables.items():
-            c = self.__dict__.get("_fused_cache", {}).get(gi)
+        caches = dict(self._pointer_caches())
+        for key, t in tables.items():
+            c = caches.get(key)
             if c is not None and c["host"].numel() == t.numel():
                 if c.get("pending") is not None:
                     c["pending"].synchronize()
                 c["host"].copy_(t)
 
-    def _step_group_fused(self, gi, group, params, step, st):
+    def _step_group_fused(self, gi, group, params, step, st, dev_state=None):
         """One launch for the group (``paradis_adamw_multi_d``).  Only the chunk list (a function of the
         parameter sizes) is cached; the four address rows (parameter, gradient, both moments) are
         rewritten every step - ``load_state_dict``, ``p.data = ...`` or ``model.to()`` replace tensors
@@ -147,10 +213,6 @@ class AdamW(torch.optim.Optimizer):
             ev.record()
             c["pending"] = ev
         b1, b2 = group["betas"]
-        dev_state = None
-        if self.capturable:
-            dev_state = self._device_state(gi, group, dev, step - 1)
-            check(lib.paradis_adamw_tick(dptr(dev_state), st), "adamw_tick")
         check(lib.paradis_adamw_multi_d(dptr(c["ptrs"]), dptr(c["numel"]), dptr(c["chunk_tensor"]),
                                       dptr(c["chunk_off"]), T, c["n_chunks"], group["lr"], b1, b2, group["eps"],
                                       group["weight_decay"], step, dptr(dev_state), st), "adamw_multi")
@@ -196,6 +258,19 @@ def _adjusted_lr(lr, shape, adjust):
     raise ValueError(f"unknown adjust_lr {adjust!r}")
 
 
+def _lr_scale(shape, adjust):
+    """``_adjusted_lr(lr, shape, adjust) / lr``: what ``paradis_muon_step_d`` multiplies the device-side lr by"""
+    import math
+    fan_out, fan_in = shape[0], math.prod(shape[1:])
+    if adjust is None:
+        return 1.0
+    if adjust == "spectral_norm":
+        return math.sqrt(fan_out / fan_in)
+    if adjust == "rms_norm":
+        return 0.2 * math.sqrt(max(fan_out, fan_in))
+    raise ValueError(f"unknown adjust_lr {adjust!r}")
+
+
 class Muon(AdamW):
     """Muon with the constructor of ``dion.Muon`` as the reference calls it (trainer.py:347-354):
     parameter groups carry ``algorithm`` ("muon" / "normuon" for 2-D-flattened weights, "adamw" for
@@ -208,7 +283,8 @@ class Muon(AdamW):
     _DEFAULT_ADJUST = "spectral_norm"
 
     def __init__(self, params, lr=0.01, mu=0.95, betas=(0.9, 0.95), weight_decay=0.01, epsilon=1e-8,
-                 nesterov=False, adjust_lr="default", flatten=False, use_triton=False, muon_beta2=0.95):
+                 nesterov=False, adjust_lr="default", flatten=False, use_triton=False, muon_beta2=0.95,
+                 capturable=False):
         del use_triton   # accepted for signature compatibility; there is no Triton on this path
         if adjust_lr == "default":
             adjust_lr = self._DEFAULT_ADJUST
@@ -217,7 +293,7 @@ class Muon(AdamW):
             params = [dict(params=params, algorithm="normuon" if self._NORMUON else "muon")]
         for gdict in params:
             gdict.setdefault("algorithm", "normuon" if self._NORMUON else "muon")
-        super().__init__(params, lr=lr, betas=betas, eps=epsilon, weight_decay=weight_decay)
+        super().__init__(params, lr=lr, betas=betas, eps=epsilon, weight_decay=weight_decay, capturable=capturable)
         for group in self.param_groups:
             group.setdefault("mu", mu)
             group.setdefault("nesterov", nesterov)
@@ -227,34 +303,33 @@ class Muon(AdamW):
 
     @torch.no_grad()
     def step(self, closure=None):
+        """the matrix groups first, then the AdamW groups; every group keeps its index in ``param_groups`` (the key of
+        its device state and of its pinned address table)"""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        adamw_groups = [g for g in self.param_groups if g["algorithm"] == "adamw"]
-        matrix_groups = [g for g in self.param_groups if g["algorithm"] != "adamw"]
-        for gi, group in enumerate(matrix_groups):
-            if group["algorithm"] not in ("muon", "normuon"):
+        indexed = list(enumerate(self.param_groups))
+        for _, group in indexed:
+            if group["algorithm"] not in ("muon", "normuon", "adamw"):
                 raise ValueError(f"unknown algorithm {group['algorithm']!r}")
-            self._step_matrix_group(gi, group)
-        if adamw_groups:
-            saved = self.param_groups
-            self.param_groups = adamw_groups
-            try:
-                AdamW.step(self)
-            finally:
-                self.param_groups = saved
+        plans = [self._prepare_matrix_group(gi, g) for gi, g in indexed if g["algorithm"] != "adamw"]
+        plans += [self._prepare_group(gi, g) for gi, g in indexed if g["algorithm"] == "adamw"]
+        self._run([pl for pl in plans if pl is not None])
         return loss
 
-    def _step_matrix_group(self, gi, group):
-        """Same-shaped matrices are updated together (one ``paradis_muon_step`` per shape: the batched
-        Newton-Schulz GEMMs fill the chip).  One device table of the w / g / momentum / variance
-        addresses serves all shapes; the gradient addresses are refreshed each step through a pinned
-        staging buffer (no host synchronisation)."""
+    def _update_group(self, pl):
+        if pl.get("matrix"):
+            self._step_matrix_group(pl)
+        else:
+            AdamW._update_group(self, pl)
+
+    def _prepare_matrix_group(self, gi, group):
         normuon = group["algorithm"] == "normuon"
         params = [p for p in group["params"] if p.grad is not None]
         if not params:
-            return
+            return None
+        steps = set()
         for p in params:
             require_hip(p, p.grad)
             if p.dim() < 2:
@@ -270,6 +345,19 @@ class Muon(AdamW):
                 if normuon:
                     state["variance_neuron"] = torch.zeros(p.shape[0], 1, dtype=p.dtype, device=p.device)
             state["step"] += 1
+            steps.add(int(state["step"]))
+        return dict(gi=gi, group=group, params=params, step=steps.pop() if len(steps) == 1 else None, dev_state=None,
+                    matrix=True)
+
+    def _step_matrix_group(self, pl):
+        """Same-shaped matrices are updated together (one ``paradis_muon_step`` per shape: the batched
+        Newton-Schulz GEMMs fill the chip).  One device table of the w / g / momentum / variance
+        addresses serves all shapes; the gradient addresses are refreshed each step through a pinned
+        staging buffer (no host synchronisation).  Capturable: the learning rate is read from the group's device
+        state (``paradis_muon_step_d``), and inside a graph capture the table copy is a graph node, as in
+        ``_step_group_fused``."""
+        gi, group, params = pl["gi"], pl["group"], pl["params"]
+        normuon = group["algorithm"] == "normuon"
         dev = params[0].device
         key = tuple((id(p), tuple(p.shape)) for p in params) + (str(dev), normuon)
         cache = self.__dict__.setdefault("_muon_cache", {})
@@ -289,7 +377,8 @@ class Muon(AdamW):
                                  table=torch.empty(4 * T, dtype=torch.int64, device=dev),
                                  ws=torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev))
         T, host = c["T"], c["host"]
-        if c.get("pending") is not None:
+        capturing = torch.cuda.is_current_stream_capturing()
+        if c.get("pending") is not None and not capturing:     # the previous step's async copy out of `host` (long done)
             c["pending"].synchronize()
         grads = []
         for p in c["order"]:
@@ -304,20 +393,31 @@ class Muon(AdamW):
                                 + [m.data_ptr() for m in mom]
                                 + ([v.data_ptr() for v in var] if normuon else [0] * T), dtype=torch.int64))
         c["table"].copy_(host, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        c["pending"] = ev
+        if capturing:
+            c["pending"] = None      # (inside a capture the copy is a graph node; nothing to wait for on the host)
+            c["captured_grads"] = grads      # every replay reads them at these addresses: they live as long as the table
+        else:
+            ev = torch.cuda.Event()
+            ev.record()
+            c["pending"] = ev
         st = stream_ptr()
         lr = group["lr"]
         base = c["table"].data_ptr()
+        split = 1 if ops.GEMM_SCHEME != ops.GEMM_EXACT else 0
         for rows, cols, full, off, n in c["shapes"]:
+            if self.capturable:
+                check(lib.paradis_muon_step_d(ctypes.c_void_p(base + 8 * off), T, n, rows, cols, lr,
+                                              _adjusted_lr(lr, full, group["adjust_lr"]), group["mu"],
+                                              group["muon_beta2"], group["weight_decay"], group["eps"],
+                                              int(bool(group["nesterov"])), int(normuon), split, dptr(c["ws"]),
+                                              dptr(pl["dev_state"]), _lr_scale(full, group["adjust_lr"]), st),
+                      "muon_step")
+                continue
             check(lib.paradis_muon_step(ctypes.c_void_p(base + 8 * off), T, n, rows, cols, lr,
                                         _adjusted_lr(lr, full, group["adjust_lr"]), group["mu"],
                                         group["muon_beta2"], group["weight_decay"], group["eps"],
-                                        int(bool(group["nesterov"])), int(normuon),
-                                        1 if ops.GEMM_SCHEME != ops.GEMM_EXACT else 0, dptr(c["ws"]), st),
+                                        int(bool(group["nesterov"])), int(normuon), split, dptr(c["ws"]), st),
                   "muon_step")
-        ops.weights_updated()
 
 
 class NorMuon(Muon):
