@@ -1,5 +1,6 @@
 // Weight-gradient kernels of the bf16-mixed scheme (PARADIS_GEMM_BF16) and their launcher pd_amp_launch_wgrad, called from
-// gemm.hip; the 128 x 128 kernel for fp32 operands is pw_gemm_wgrad_split_kernel<1> of gemm_common.h.
+// gemm.hip with the plan (WgradKind::Amp128 / Tall / Square); the 128 x 128 kernel for fp32 operands is
+// pw_gemm_wgrad_split_kernel<1> of gemm_common.h.
 #include "gemm_common.h"
 
 namespace {
@@ -146,8 +147,7 @@ pw_gemm_wgrad_b16_kernel(GemmArgs g) {
 // only, of X; A16 / B16 = the operand is stored as bf16 (one 16-byte load is the LDS chunk) or as fp32 (two loads,
 // rounded in registers); otherwise the pipeline of pw_gemm_wgrad_b16_kernel: loads two tiles ahead, one barrier per tile,
 // K-range slabs with alternating sign, fused row sums.
-constexpr int TALL_PA = 256 + 8, TALL_PB = 128 + 8, TALL_STAGE = 2 * TALL_PA + 2 * TALL_PB;   // chunks
-constexpr size_t tall_lds_bytes() { return (size_t)2 * TALL_STAGE * 16; }
+// (row pitches TALL_PA / TALL_PB, TALL_STAGE chunks per stage and tall_lds_bytes(): gemm_common.h, beside the plan)
 template <bool A16, bool B16>
 __global__ void __launch_bounds__(512, 4)
 pw_gemm_wgrad_tall_kernel(GemmArgs g) {
@@ -291,8 +291,7 @@ pw_gemm_wgrad_tall_kernel(GemmArgs g) {
 // (two waves per SIMD: enough for a kernel that waits on L2 bytes, not on the matrix pipe); every thread stages one chunk of
 // each operand.  1024 x 1024, bf16 operands: 296 us (128 x 128) -> 250 (256 x 128) -> 221 (256 x 256).  PARADIS_WGRAD_SQUARE=0 /
 // PARADIS_WGRAD_TALL=0 select the smaller tiles (A/B runs).
-constexpr int SQ_P = 256 + 8, SQ_STAGE = 4 * SQ_P;   // chunks
-constexpr size_t sq_lds_bytes() { return (size_t)4 * SQ_STAGE * 16; }
+// (row pitch SQ_P, SQ_STAGE chunks per stage and sq_lds_bytes(): gemm_common.h)
 template <bool A16, bool B16>
 __global__ void __launch_bounds__(512, 2)
 pw_gemm_wgrad_square_kernel(GemmArgs g) {
@@ -461,14 +460,12 @@ constexpr GemmKernel WGRAD_128[4] = {&pw_gemm_wgrad_split_kernel<1>, &pw_gemm_wg
 }  // namespace
 
 // ---- launcher of the bf16-mixed weight-gradient kernels (called from gemm.hip) ------------------------------------------
-int pd_amp_launch_wgrad(const GemmArgs& g0, int io16, int kind, int grid, hipStream_t st) {
+int pd_amp_launch_wgrad(const GemmArgs& g0, int io16, const WgradPlan& p, hipStream_t st) {
   GemmArgs g = g0;
   g.io16 = io16;
-  constexpr size_t lds128 = (size_t)2 * 2 * simgp(1) * 16;
   const bool a16 = (io16 & IO_A16) != 0, b16 = (io16 & IO_B16) != 0;
-  if (kind == 3) return launch_io2<WGRAD_SQUARE>(a16, b16, dim3(grid), dim3(512), sq_lds_bytes(), "pw_gemm_wgrad(square)", st, g);
-  if (kind == 2) return launch_io2<WGRAD_TALL>(a16, b16, dim3(grid), dim3(512), tall_lds_bytes(), nullptr, st, g);
-  // kind 1 without a bf16 dY takes X as bf16 whatever io16 says: there is no pw_gemm_wgrad_b16_kernel<false, false>
-  if (kind == 1) return launch_io2<WGRAD_128>(a16, b16 || !a16, dim3(grid), dim3(256), lds128, nullptr, st, g);
-  return launch_io2<WGRAD_128>(false, false, dim3(grid), dim3(256), lds128, nullptr, st, g);
+  const dim3 grid(p.grid), block(p.block);
+  if (p.kind == WgradKind::Square) return launch_io2<WGRAD_SQUARE>(a16, b16, grid, block, p.lds, "pw_gemm_wgrad(square)", st, g);
+  if (p.kind == WgradKind::Tall) return launch_io2<WGRAD_TALL>(a16, b16, grid, block, p.lds, nullptr, st, g);
+  return launch_io2<WGRAD_128>(a16, b16, grid, block, p.lds, nullptr, st, g);      // Amp128
 }

@@ -1,8 +1,13 @@
-// What the three translation units of the pointwise GEMMs share: gemm.hip (the fp32-width schemes and the C ABI),
-// gemm_amp_fwd.hip and gemm_amp_wgrad.hip (the bf16-mixed scheme's forward / data-gradient and weight-gradient kernels).
+// What the five translation units of the pointwise GEMMs share: gemm.hip (the C ABI's GEMM entry points, the weight
+// gradient's slab reduction), gemm_exact.hip (the f32-MFMA kernels and their tunables), gemm_split.hip (the split-operand
+// kernels and the weight images' entry points), gemm_amp_fwd.hip and gemm_amp_wgrad.hip (the bf16-mixed scheme's forward /
+// data-gradient and weight-gradient kernels).
 // Arguments, tile constants, the epilogue, the split / round helpers, the one kernel template that two units instantiate
-// (pw_gemm_wgrad_split_kernel) and the launch helpers.  Everything below the declarations sits in an anonymous namespace.
+// (pw_gemm_wgrad_split_kernel), the launch helpers and - host only, at the end - the weight gradient's plan (wgrad_plan).
+// Everything below the declarations sits in an anonymous namespace.
 #pragma once
+#include <algorithm>
+#include <cstdlib>
 #include <initializer_list>
 #include "common.h"
 
@@ -36,10 +41,46 @@ struct GemmArgs {
   //  before the fp32 residual / blend; a compile-time property of pw_gemm_bf16_k32_kernel's epilogue.  Stored as fp32.)
 };
 
-// launchers of the bf16-mixed kernels (gemm_amp_fwd.hip, gemm_amp_wgrad.hip; called from gemm.hip)
+// The weight-gradient kernels, one per schedule (wgrad_plan below picks one):
+//   Staged  pw_gemm_kernel<true, true, BK>      f32 MFMA, operands staged through registers; any shape, no fused row sums
+//   Dma     pw_gemm_wgrad_dma_kernel            f32 MFMA, LDS-DMA
+//   Bf16x3  pw_gemm_wgrad_split_kernel<3>       six bf16 products          F16x2  pw_gemm_wgrad_split_kernel<2>
+//   Amp128 / Tall / Square                      bf16-mixed scheme on a 128 x 128, 256 x 128, 256 x 256 tile
+enum class WgradKind { Staged, Dma, Bf16x3, F16x2, Amp128, Tall, Square };
+// the workspace: [S][M,K] slabs, then [S][M] row-sum partials (S = 1: the slab area is unused, the GEMM writes dW)
+struct WgradWorkspace {
+  int S, M, K;
+  size_t rowsum_offset() const { return (size_t)S * M * K; }      // floats
+  size_t bytes() const { return (size_t)S * M * ((size_t)K + 1) * sizeof(float) + 256; }
+  float* rowsums(void* ws) const { return (float*)ws + rowsum_offset(); }
+};
+
+struct WgradPlan {
+  WgradKind kind;
+  int S;                  // K-range slabs = grid batches
+  int grid, block;
+  size_t lds;
+  bool fused_rowsums;     // the kernel also sums the rows of dY per slab (else: a separate paradis_bias_grads pass)
+  bool to_slabs;          // the GEMM writes S slabs for slab_reduce_kernel (else: dW itself)
+  WgradWorkspace ws;
+};
+
+// gemm_exact.hip: its tunables by value, and its launchers (a_kc / b_kc: the operand is k-contiguous)
+struct GemmTunables { int bk, wg_per_cu, stagger, dma_stages, wgrad_dma_stages; };
+GemmTunables pd_exact_tunables();
+int pd_exact_launch(bool a_kc, bool b_kc, const GemmArgs& g, int grid, hipStream_t st);
+bool pd_exact_dma_eligible(const GemmArgs& g);
+int pd_exact_launch_dma(const GemmArgs& g, int grid, hipStream_t st);
+int pd_exact_launch_wgrad(const GemmArgs& g, const WgradPlan& p, hipStream_t st);      // Staged, Dma
+// gemm_split.hip.  scheme: PARADIS_GEMM_BF16X3 or PARADIS_GEMM_F16X2 (the latter with d.a_amax / d.b_amax set)
+int pd_split_launch(const GemmArgs& d, int scheme, hipStream_t st);
+int pd_split_launch_wgrad(const GemmArgs& g, const WgradPlan& p, hipStream_t st);      // Bf16x3, F16x2
+int64_t pd_split_image_chunks(int M, int K, int np);
+// bf16x3 images of nbatch row-major [M,K] matrices (stride a_bs) into out, pd_split_image_chunks(M, K, 3) chunks each
+void pd_split_launch_images(const float* A, int nbatch, int M, int K, int64_t a_bs, void* out, hipStream_t st);
+// launchers of the bf16-mixed kernels (gemm_amp_fwd.hip, gemm_amp_wgrad.hip)
 int pd_amp_launch_fwd(const GemmArgs& d, hipStream_t st);
-// kind: 0 = 128 x 128 tile, fp32 operands; 1 = 128 x 128 with a bf16 operand; 2 = 256 x 128; 3 = 256 x 256 (grid: the caller's)
-int pd_amp_launch_wgrad(const GemmArgs& g, int io16, int kind, int grid, hipStream_t st);
+int pd_amp_launch_wgrad(const GemmArgs& g, int io16, const WgradPlan& p, hipStream_t st);      // Amp128, Tall, Square
 
 namespace {
 
@@ -603,7 +644,7 @@ __device__ __forceinline__ void split_unscale(f32x16 (&acc)[2][2], float inv_a, 
       for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] * inv_a) * inv_b;
 }
 
-// ---- the weight-gradient kernel of the split schemes: gemm.hip launches NP = 3 and 2, gemm_amp_wgrad.hip NP = 1 ---------
+// ---- the weight-gradient kernel of the split schemes: gemm_split.hip launches NP = 3 and 2, gemm_amp_wgrad.hip NP = 1 ---
 // wgrad: dW[M,N'] = sum over (sample, p) A[m][p] B[n][p], both operands p-contiguous fp32, both split
 // in registers.  Thread t stages 8 consecutive p of row t>>1 (k-half t&1) of each operand.
 // Needs K % 16 == 0 and 16-B aligned rows (host-checked; otherwise the f32 kernels run).
@@ -762,15 +803,17 @@ typedef void (*GemmKernel)(GemmArgs);
 // the four instantiations of a kernel template over two I/O-type flags, indexed a + 2 * b
 #define IO2_KERNELS(K) {&K<false, false>, &K<true, false>, &K<false, true>, &K<true, true>}
 
-// a dynamic-LDS request above 64 KiB has to be granted per kernel and device: `bytes` on every kernel of `ks`, once
-// per device (`once`: one per kernel family)
+// a dynamic-LDS request above 64 KiB has to be granted per kernel and device
+inline int reserve_lds(GemmKernel k, size_t bytes, const char* what) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return 0;
+  paradis_set_error("%s: cannot reserve LDS", what);
+  return 2;
+}
+// ... `bytes` on every kernel of `ks`, once per device (`once`: one per kernel family)
 inline int reserve_lds(PerDeviceOnce& once, std::initializer_list<GemmKernel> ks, size_t bytes, const char* what) {
   if (!once.first()) return 0;
   for (GemmKernel k : ks)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-      paradis_set_error("%s: cannot reserve LDS", what);
-      return 2;
-    }
+    if (int e = reserve_lds(k, bytes, what)) return e;
   return 0;
 }
 
@@ -783,5 +826,142 @@ int launch_io2(bool a, bool b, dim3 grid, dim3 block, size_t lds, const char* re
     if (int e = reserve_lds(once, {KS[0], KS[1], KS[2], KS[3]}, lds, reserve_for)) return e;
   hipLaunchKernelGGL(KS[a + 2 * b], grid, block, lds, st, g);
   return 0;
+}
+
+// A kernel family as ONE constexpr table indexed by its template parameters: the launch indexes it, the reservation walks
+// it (`once`: one per table).  lds: the dynamic LDS the entry's launches may ask for, reserved if above 64 KiB; k == nullptr:
+// a combination of parameters that nobody instantiates.
+struct GemmKernelEntry { GemmKernel k; size_t lds; };
+template <int N>
+int reserve_lds(PerDeviceOnce& once, const GemmKernelEntry (&tab)[N], const char* what) {
+  bool any = false;
+  for (const GemmKernelEntry& e : tab) any = any || (e.k && e.lds > 64 * 1024);
+  if (!any || !once.first()) return 0;
+  for (const GemmKernelEntry& e : tab)
+    if (e.k && e.lds > 64 * 1024)
+      if (int err = reserve_lds(e.k, e.lds, what)) return err;
+  return 0;
+}
+// launch entry i with the entry's LDS bytes, or with `lds` of them if given (a request that varies at run time)
+template <int N>
+int launch_entry(const GemmKernelEntry (&tab)[N], int i, PerDeviceOnce& once, const char* what, int grid, int block,
+                 hipStream_t st, const GemmArgs& g, size_t lds = 0) {
+  if (i < 0 || i >= N || tab[i].k == nullptr) { paradis_set_error("%s: no kernel for index %d", what, i); return 1; }
+  if (int e = reserve_lds(once, tab, what)) return e;
+  hipLaunchKernelGGL(tab[i].k, dim3(grid), dim3(block), lds ? lds : tab[i].lds, st, g);
+  return 0;
+}
+
+// ---- host side: LDS bytes of the weight-gradient kernels (their launchers and the plan below) --------------------------------
+constexpr int DBK = 16;                 // k-tile depth of the LDS-DMA f32 kernels (gemm_exact.hip)
+constexpr int DTILE = DBK * BM;         // floats per operand per stage (pitch 128, unpadded)
+constexpr size_t dma_lds_bytes(int stages) { return (size_t)stages * 2 * DTILE * sizeof(float); }
+// register-staged f32 kernel: floats per operand per stage (upper bound), bytes of its two stages, and what a launch asks
+// for - the dynamic-LDS request doubles as the occupancy control: 160 KiB / request = workgroups per CU
+constexpr int stage_floats(int bk) { return bk * (BM + 4); }
+constexpr size_t lds_bytes(int bk) { return (size_t)4 * stage_floats(bk) * sizeof(float); }
+constexpr size_t STAGED_LDS_MAX = 160 * 1024;
+inline size_t staged_lds_request(int bk, int wg_per_cu) {
+  return std::min(std::max(lds_bytes(bk), (size_t)(160 * 1024 / wg_per_cu) & ~(size_t)255), STAGED_LDS_MAX);
+}
+constexpr size_t split_lds_wgrad(int np) { return (size_t)2 * 2 * simgp(np) * 16; }
+// bf16-mixed 256 x 128 and 256 x 256 tiles (gemm_amp_wgrad.hip): row pitches and stage sizes in chunks
+constexpr int TALL_PA = 256 + 8, TALL_PB = 128 + 8, TALL_STAGE = 2 * TALL_PA + 2 * TALL_PB;
+constexpr size_t tall_lds_bytes() { return (size_t)2 * TALL_STAGE * 16; }
+constexpr int SQ_P = 256 + 8, SQ_STAGE = 4 * SQ_P;
+constexpr size_t sq_lds_bytes() { return (size_t)4 * SQ_STAGE * 16; }
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- the weight gradient's plan: dW[M,K] = sum_b dY[b][M,N] . X[b][K,N]^T ---------------------------------------------------
+// ONE place decides which kernel runs, how many K-range slabs it writes, its launch geometry, whether it fuses the bias
+// gradient's row sums and where slabs and row sums live in the workspace.  paradis_pw_gemm_wgrad launches from it,
+// paradis_pw_gemm_wgrad_ws_bytes / _slabs ask it, tools/gemm_plan_check.hip holds it against the rules it replaced.
+// Host only: nothing here touches the device.
+
+// PARADIS_WGRAD_TALL=0 / PARADIS_WGRAD_SQUARE=0 switch the bf16-mixed scheme's larger tiles off (A/B runs); read once
+struct WgradEnv { bool tall, square; };
+inline WgradEnv wgrad_env() {
+  static const WgradEnv env = [] {
+    const char *t = getenv("PARADIS_WGRAD_TALL"), *s = getenv("PARADIS_WGRAD_SQUARE");
+    return WgradEnv{!(t && t[0] == '0'), !(s && s[0] == '0')};
+  }();
+  return env;
+}
+
+// output tile, k depth, resident workgroups per CU, threads and dynamic LDS of a kind's kernel
+struct WgradTile { int th, tw, kd, wg_per_cu, block; size_t lds; };
+inline WgradTile wgrad_tile(WgradKind kind, const GemmTunables& t) {
+  switch (kind) {
+    case WgradKind::Staged: return {BM, BN, t.bk, t.wg_per_cu, 256, staged_lds_request(t.bk, t.wg_per_cu)};
+    case WgradKind::Dma:    return {BM, BN, DBK, t.wgrad_dma_stages == 2 ? 4 : 3, 256, dma_lds_bytes(t.wgrad_dma_stages)};
+    case WgradKind::Bf16x3: return {BM, BN, SBK, 3, 256, split_lds_wgrad(3)};
+    case WgradKind::F16x2:  return {BM, BN, SBK, 3, 256, split_lds_wgrad(2)};
+    case WgradKind::Amp128: return {BM, BN, SBK, 3, 256, split_lds_wgrad(1)};
+    case WgradKind::Tall:   return {256, BN, SBK, 2, 512, tall_lds_bytes()};
+    case WgradKind::Square: return {256, 256, SBK, 1, 512, sq_lds_bytes()};
+  }
+  return {};
+}
+constexpr WgradKind WGRAD_KINDS[] = {WgradKind::Staged, WgradKind::Dma,  WgradKind::Bf16x3, WgradKind::F16x2,
+                                     WgradKind::Amp128, WgradKind::Tall, WgradKind::Square};
+
+// number of K-range slabs: one round of resident workgroups over the 256 CUs
+inline int wgrad_splits(int B, int M, int K, int N, const WgradTile& tl) {
+  const int tiles = ((M + tl.th - 1) / tl.th) * ((K + tl.tw - 1) / tl.tw);
+  const int64_t total_kt = (int64_t)B * ((N + tl.kd - 1) / tl.kd);
+  int s = (int)std::max<int64_t>(1, std::min<int64_t>(256 * tl.wg_per_cu / tiles, total_kt));
+  // the split kernels accumulate alternate slabs with opposite sign so that the bf16 MFMA's alignment offset cancels
+  // in the slab sum ("sign checkerboard"): that takes an even number of slabs (1536 x 384: 21 -> 20; round 5)
+  if (s > 1) s &= ~1;
+  return s;
+}
+
+// the tile wastes at most ~1/7 of its 256 rows / columns
+inline bool wgrad_fills_256(int n) { return ((n + 255) / 256) * 256 * 7 <= n * 8; }
+
+// dy_bs / x_bs: sample strides in elements; dY / X: alignment only
+inline WgradKind wgrad_kind(int M, int K, int N, int64_t dy_bs, int64_t x_bs, const void* dY, const void* X, int scheme,
+                            int io16, const GemmTunables& t, WgradEnv env) {
+  // both operands p-contiguous with whole, 16-B aligned 16-float chunks (LDS-DMA and split kernels)
+  const bool vec = N % DBK == 0 && (dy_bs & 3) == 0 && (x_bs & 3) == 0 && aligned16(dY) && aligned16(X);
+  // a split scheme: both operands are split in registers; bf16-stored operands (io16) were checked by the caller
+  if (io16 != 0 || (scheme != PARADIS_GEMM_EXACT && vec)) {
+    if (scheme == PARADIS_GEMM_BF16) {
+      const bool tall = env.tall && M >= 256 && wgrad_fills_256(M);
+      return tall && env.square && wgrad_fills_256(K) ? WgradKind::Square : tall ? WgradKind::Tall : WgradKind::Amp128;
+    }
+    return scheme == PARADIS_GEMM_F16X2 ? WgradKind::F16x2 : WgradKind::Bf16x3;
+  }
+  return t.wgrad_dma_stages >= 2 && vec ? WgradKind::Dma : WgradKind::Staged;
+}
+
+inline WgradPlan wgrad_plan_of(WgradKind kind, int B, int M, int K, int N, const GemmTunables& t) {
+  const WgradTile tl = wgrad_tile(kind, t);
+  const int S = wgrad_splits(B, M, K, N, tl), grid = ((M + tl.th - 1) / tl.th) * ((K + tl.tw - 1) / tl.tw) * S;
+  return {kind, S, grid, tl.block, tl.lds, kind != WgradKind::Staged, S > 1, {S, M, K}};
+}
+
+inline WgradPlan wgrad_plan(int B, int M, int K, int N, int64_t dy_bs, int64_t x_bs, const void* dY, const void* X, int scheme,
+                            int io16, const GemmTunables& t, WgradEnv env) {
+  return wgrad_plan_of(wgrad_kind(M, K, N, dy_bs, x_bs, dY, X, scheme, io16, t, env), B, M, K, N, t);
+}
+
+// Workspace bytes for a shape: the largest over EVERY kind.  The query sees neither pointers, strides, scheme nor the
+// switches, and the value is part of what callers (ops.py, muon.hip) size buffers from: it stays what it always was.
+inline size_t wgrad_ws_bytes(int B, int M, int K, int N, const GemmTunables& t) {
+  size_t bytes = 0;
+  for (WgradKind kind : WGRAD_KINDS) bytes = std::max(bytes, wgrad_plan_of(kind, std::max(B, 1), M, K, N, t).ws.bytes());
+  return bytes;
+}
+
+// slab_reduce_kernel's launch: slab sums in a fixed order over blocks1 workgroups (n = 0: one slab, the GEMM wrote dW itself),
+// the row sums' reduction riding along in blocks2 more
+struct SlabReduce { int64_t n; int vec, blocks1, n2, blocks2; };
+inline SlabReduce wgrad_reduce(const WgradPlan& p, const void* workspace, const void* dW, bool rowsums) {
+  const int64_t n = p.to_slabs ? (int64_t)p.ws.M * p.ws.K : 0;
+  const int vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(dW)) & 15) == 0;
+  const int n2 = rowsums ? p.ws.M : 0;
+  return {n, vec, n ? (int)std::min<int64_t>(((vec ? n / 4 : n) + 255) / 256, 2048) : 0, n2, (n2 + 255) / 256};
 }
 }  // namespace

@@ -127,6 +127,31 @@ def test_dwconv_workspace_sizes_and_bf16_cotangent_grids_are_pinned():
         assert _lib.lib.paradis_dwconv_geo_wgrad_ws_bytes(B, C, H, W, k) == nbytes, (B, C, H, W, k)
 
 
+# (B, Co, Ci, P) -> paradis_pw_gemm_wgrad_ws_bytes, paradis_pw_gemm_wgrad_slabs; recorded from the library before the
+# weight gradient's schedule moved into one plan (csrc/gemm_common.h wgrad_plan): ops.py and muon.hip size buffers from them
+_WGRAD_HOST = [
+    ((2, 5, 3, 60), 896, 8),                   # the shapes of test_wgrad_every_kind_exact: register-staged
+    ((2, 5, 3, 64), 896, 8),                   # ... LDS-DMA and split kernels
+    ((1, 5, 3, 16), 336, 1),                   # ... one k-tile: one slab
+    ((2, 256, 8, 32), 37120, 4),               # ... the 256 x 128 tile
+    ((2, 448, 8, 32), 64768, 4),               # ... with a ragged second tile
+    ((2, 256, 224, 32), 921856, 4),            # ... the 256 x 256 tile
+    ((4, 1536, 384, 2048), 66232576, 20),      # 768 / 36 tiles = 21 -> 20
+    ((0, 64, 48, 128), 100608, 8),             # empty batch: sized as one sample
+    ((1, 1024, 1024, 721 * 1440), 67174656, 12),   # 0.25 degree grid
+    ((4, 2560, 2560, 2048), 52449536, 1),      # 400 tiles, beyond 384: one slab
+    ((1, 97, 768, 16), 298628, 1),
+    ((32, 2048, 1536, 2048), 50364672, 4),
+]
+
+
+def test_wgrad_workspace_sizes_and_slab_counts_are_pinned():
+    from paradis_model_amd import _lib
+    for shape, nbytes, slabs in _WGRAD_HOST:
+        assert _lib.lib.paradis_pw_gemm_wgrad_ws_bytes(*shape) == nbytes, shape
+        assert _lib.lib.paradis_pw_gemm_wgrad_slabs(*shape) == slabs, shape
+
+
 def test_ops_refuse_cpu_tensors():
     from paradis_model_amd import feed, ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):
@@ -276,7 +301,7 @@ def test_weight_image_cache_invalidation():
 def test_weight_gradient_slab_count_is_even_or_one():
     """The weight gradient cancels the offset between K-range slabs of alternating sign, which needs an even number of
     them.  The host picks the slab count from the tile count (768 resident workgroups / tiles): 1536 x 384 would get 21.
-    It is rounded down to an even number (csrc/gemm.hip wgrad_splits); one slab (weight matrices beyond 384 tiles, none in
+    It is rounded down to an even number (csrc/gemm_common.h wgrad_splits); one slab (weight matrices beyond 384 tiles, none in
     this model) has no partner and keeps the offset - documented, not cancelled."""
     from paradis_model_amd._lib import lib
     shapes = [(1024, 186), (384, 1024), (1536, 384), (768, 1024), (1024, 768), (1024, 1024), (896, 1152), (896, 896),

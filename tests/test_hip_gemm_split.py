@@ -331,7 +331,7 @@ def test_f16x2_is_opt_in_and_traceable(ops):
 # WITHOUT the checkerboard (-DSPLIT_SIGNED=0) carries the same offset on every output: mean signed error -0.9 u
 # (y, dX) and -8 u (dW, 32,768-term sums) under 8 / 14 u of zero-mean noise; the f32 MFMA: +0.002 u.  With the
 # checkerboard the plain mean is 0.000 u (dW: -0.006 u).  These tests fail on a -DSPLIT_SIGNED=0 build
-# (verified on the GPU box with tools/build_variant.sh nosign "gemm.hip gemm_amp_fwd.hip gemm_amp_wgrad.hip" "-DSPLIT_SIGNED=0").
+# (verified on the GPU box with tools/build_variant.sh nosign "gemm_split.hip gemm_amp_fwd.hip gemm_amp_wgrad.hip" "-DSPLIT_SIGNED=0").
 # Reference sums that exposed it: reference model/blocks.py:129-133 (ChannelNorm statistics and parameter gradients).
 # ---------------------------------------------------------------------------------------------------------------
 LAYER_SHAPES = [(1024, 186), (384, 1024), (1536, 384), (768, 1024), (1024, 768), (1024, 1024), (896, 1152),

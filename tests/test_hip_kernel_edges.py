@@ -12,7 +12,10 @@ ordinary order, measured on the reference side only.  Every figure is printed (`
 
 Input design: the first and last element of each reduced range and the last element in front of each chunk / tile
 boundary of the source are 2^10 times the rest, so a dropped or doubled one is seen; at least one case per kernel has
-strictly positive terms, so nothing cancels."""
+strictly positive terms, so nothing cancels.
+
+The weight gradient of the pointwise GEMMs closes the file: one call per kernel its plan (csrc/gemm_common.h, wgrad_plan)
+can choose, on integer-valued operands, against fp64 with tolerance zero."""
 import json
 import os
 import subprocess
@@ -744,3 +747,56 @@ def test_adamw(record_property, mode):
         J.add(f"m[{sizes[i]}]", sm["exp_avg"], m1, sc["exp_avg"], ADAM)
         J.add(f"v[{sizes[i]}]", sm["exp_avg_sq"], v1, sc["exp_avg_sq"], ADAM)
     J.done()
+
+
+# ---- the pointwise GEMMs' weight gradient, once per kernel of its plan --------------------------------------------------
+# (scheme, dz stored as bf16, x stored as bf16, B, Co, Ci, H, W, x is a channel slice of a wider tensor); each shape is the
+# smallest that reaches its kernel by the predicates of wgrad_kind (csrc/gemm_common.h) - tools/gemm_plan_check.hip prints
+# the kernel it picks for every one of them and fails unless all seven occur
+_WGRAD_KINDS = {
+    "register-staged (P % 16 != 0)":     ("exact", False, False, 2, 5, 3, 6, 10, False),
+    "f32 DMA":                           ("exact", False, False, 2, 5, 3, 8, 8, False),
+    "f32 DMA, one slab":                 ("exact", False, False, 1, 5, 3, 4, 4, False),
+    "f32 DMA, sliced x":                 ("exact", False, False, 2, 5, 3, 8, 8, True),
+    "bf16x3 split":                      ("bf16x3", False, False, 2, 5, 3, 8, 8, False),
+    "bf16x3 split, one slab":            ("bf16x3", False, False, 1, 5, 3, 4, 4, False),
+    "bf16x3 split, sliced x":            ("bf16x3", False, False, 2, 5, 3, 8, 8, True),
+    "f16x2 split":                       ("f16x2", False, False, 2, 5, 3, 8, 8, False),
+    "f16x2 split, one slab":             ("f16x2", False, False, 1, 5, 3, 4, 4, False),
+    "bf16-mixed 128x128, fp32 operands": ("bf16", False, False, 2, 5, 3, 8, 8, False),
+    "bf16-mixed 128x128, bf16 dz":       ("bf16", True, False, 2, 5, 3, 8, 8, False),
+    "bf16-mixed 128x128, bf16 x":        ("bf16", False, True, 2, 5, 3, 8, 8, False),
+    "bf16-mixed 128x128, both bf16":     ("bf16", True, True, 2, 5, 3, 8, 8, False),
+    "tall":                              ("bf16", False, False, 2, 256, 8, 4, 8, False),
+    "tall, ragged second tile":          ("bf16", False, False, 2, 448, 8, 4, 8, False),
+    "tall, sliced bf16 x":               ("bf16", False, True, 2, 256, 8, 4, 8, True),
+    "square":                            ("bf16", False, False, 2, 256, 224, 4, 8, False),
+}
+
+
+@pytest.mark.parametrize("kind", list(_WGRAD_KINDS))
+def test_wgrad_every_kind_exact(ops, kind):
+    """dW = sum_b dz x^T and the bias gradient (row sums of dz) through ops.RAW["pw_gemm_wgrad"], once per kernel the
+    plan can choose.  Operands are integers in [-4, 4]: exact as bf16, every product and every partial sum an integer of
+    magnitude <= 16 B P < 2^24, so fp32 accumulation in any order, the slab sums and the f16x2 scheme's power-of-two
+    scaling are all exact - the tolerance against fp64 is zero by construction, not by measurement (the method of
+    test_split_exactness_on_bf16_representable_inputs)."""
+    scheme, dz16, x16, B, Co, Ci, H, W, sliced = _WGRAD_KINDS[kind]
+    assert 16 * B * H * W < 2 ** 24
+    g = torch.Generator().manual_seed(Co * 1000 + Ci + H)
+    dz = torch.randint(-4, 5, (B, Co, H, W), generator=g).float().cuda()
+    wide = torch.randint(-4, 5, (B, Ci + 2, H, W), generator=g).float().cuda()
+    if dz16:
+        dz = dz.bfloat16()
+    if x16:
+        wide = wide.bfloat16()
+    x = wide[:, 1:1 + Ci] if sliced else wide[:, 1:1 + Ci].contiguous()
+    assert sliced == (B > 1 and x.stride(0) != Ci * H * W)
+    code = {"exact": ops.GEMM_EXACT, "bf16": ops.GEMM_BF16, "f16x2": ops.GEMM_F16X2, "bf16x3": ops.GEMM_BF16X3}[scheme]
+    gw, gb = ops.RAW["pw_gemm_wgrad"](dz, x, True, None, None, code)
+    torch.cuda.synchronize()
+    ref_w = torch.einsum("bmhw,bkhw->mk", dz.double(), x.double())
+    ref_b = dz.double().sum(dim=(0, 2, 3))
+    assert gw.dtype == torch.float32 and gw.shape == (Co, Ci) and gb.shape == (Co,)
+    assert torch.equal(gw.double(), ref_w), (kind, float((gw.double() - ref_w).abs().max()))
+    assert torch.equal(gb.double(), ref_b), (kind, float((gb.double() - ref_b).abs().max()))

@@ -1,14 +1,14 @@
 #!/bin/bash
 # Diagnostic: A/B two builds of libparadis_hip.so on ONE box at the level of the training step
 # (box-to-box spread is ~4 %, isolated-kernel A/Bs do not always carry over to the step).
-#   tools/ab_step.sh "<extra hipcc flags for the three GEMM units (gemm*.hip) of build B>" [rounds]
+#   tools/ab_step.sh "<extra hipcc flags for the GEMM units (gemm*.hip) of build B>" [rounds]
 # Run the build part locally (no GPU needed), the measuring part through gpurun.
 FLAGS=$1; ROUNDS=${2:-3}
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/build/ab; mkdir -p $OUT
 if ! python3 -c "import torch,sys; sys.exit(0 if torch.cuda.is_available() else 1)" 2>/dev/null; then
   OBJS=$(ls $R/build/obj/*.o | grep -v "/gemm[a-z_]*\.o")
-  for u in gemm gemm_amp_fwd gemm_amp_wgrad; do
+  for u in gemm gemm_exact gemm_split gemm_amp_fwd gemm_amp_wgrad; do
     /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -munsafe-fp-atomics -fno-slp-vectorize $FLAGS \
         -c $R/paradis_model_amd/csrc/$u.hip -o $OUT/${u}_b.o || exit 1
     OBJS="$OBJS $OUT/${u}_b.o"

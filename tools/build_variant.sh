@@ -1,8 +1,9 @@
 #!/bin/bash
 # Diagnostic: build build/variants/lib_<name>.so = the shipped library with the named sources recompiled with extra flags
 #   tools/build_variant.sh <name> "<source.hip ...>" "<extra hipcc flags>"        (runs without a GPU)
-# A macro that several units read takes all of them: SPLIT_SIGNED sits in gemm_common.h, so
-#   tools/build_variant.sh nosign "gemm.hip gemm_amp_fwd.hip gemm_amp_wgrad.hip" "-DSPLIT_SIGNED=0"
+# A macro that several units read takes all of them: SPLIT_SIGNED sits in gemm_common.h and is read by the units with
+# split or bf16-mixed kernels (gemm.hip and gemm_exact.hip have none), so
+#   tools/build_variant.sh nosign "gemm_split.hip gemm_amp_fwd.hip gemm_amp_wgrad.hip" "-DSPLIT_SIGNED=0"
 # and the ADV_* knobs sit in advect_common.h, so an advection variant takes all four advect units:
 #   tools/build_variant.sh halo12 "advect.hip advect_planes.hip advect_tilerow.hip advect_strips.hip" "-DADV_HALO_BWD=12"
 # Likewise the DWCONV_* knobs sit in stencil_common.h, so a stencil variant takes all three stencil units:
