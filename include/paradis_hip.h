@@ -235,9 +235,9 @@ int paradis_dwconv_geo_fwd16(const float* x, const float* w, const float* bias, 
                              int W, int k, void* stream);
 /* ... and their backward reading the cotangent of that bf16 output as a bf16 tensor - the consumer's data gradient, bf16-valued in
  * the reference's autocast backward as well.  Same arguments as paradis_channel_norm_bwd / paradis_dwconv_geo_bwd otherwise; every
- * result fp32 and bit-identical to the fp32 entry point on the widened cotangent.  Supported where the *_ok query returns 1 (the
- * streaming ChannelNorm kernels: every practical shape; the whole-plane stencil kernel: k = 5, W = 64, H <= 32); elsewhere the
- * call fails with rc 1 and the caller widens gy. */
+ * result fp32 and bit-identical to the fp32 entry point on the widened cotangent.  Supported where the *_ok query returns 1
+ * (ChannelNorm: exactly the shapes paradis_channel_norm_bwd accepts; the whole-plane stencil kernel: k = 5, W = 64, H <= 32);
+ * elsewhere the call fails with rc 1 (a stencil caller widens gy; a ChannelNorm shape has no other route). */
 int paradis_channel_norm_bwd16_ok(int B, int C, int P);
 int paradis_channel_norm_bwd16(const void* gy /* bf16 */, const float* x1, const float* x2, const float* w, const float* mean,
                                const float* rstd, float* gx1, float* gx2, float* gw, float* gb, int B, int C1, int C2, int P,
@@ -262,7 +262,10 @@ size_t paradis_channel_norm_bwd_ws_bytes(int B, int C, int P);
 /* gx1/gx2 receive the slices of the input gradient (gx2 may be NULL); gw,gb [C].
  * addend1 (optional, [B,C1,P] with batch stride add1_bs) is added to gx1: the gradient that reaches
  * x1 through the residual connection around the block (paradis.py:246,253), so autograd's separate
- * accumulation pass disappears. */
+ * accumulation pass disappears.
+ * One schedule (two streaming kernels, fixed-order finish) whose apply grid is B * (C1 + C2) * ceil(P / 8192) workgroups:
+ * a shape at which that product reaches 2^31 - a cotangent of 8 GiB or more - is refused with rc 1 ("too large").
+ * workspace: paradis_channel_norm_bwd_ws_bytes(B, C1 + C2, P) bytes, 16-byte aligned for the 16-byte path. */
 int paradis_channel_norm_bwd(const float* gy, const float* x1, const float* x2, const float* w,
                              const float* mean, const float* rstd, float* gx1, float* gx2,
                              float* gw, float* gb, int B, int C1, int C2, int P,

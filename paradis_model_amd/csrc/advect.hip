@@ -112,8 +112,7 @@ int check_adv(const char* name, int B, int K, int H, int W, int mode) {
 
 // 16-byte staging path: aligned planes, p even (bicubic), padded width even
 int adv_vec4(const float* field, int H, int W, int64_t f_bs, int p) {
-  return (W % 4 == 0) && (f_bs % 4 == 0) && (((int64_t)H * W) % 4 == 0) && (p % 2 == 0) &&
-         (reinterpret_cast<uintptr_t>(field) & 15) == 0;
+  return (W % 4 == 0) && (f_bs % 4 == 0) && (((int64_t)H * W) % 4 == 0) && (p % 2 == 0) && aligned16(field);
 }
 
 // ---- the schedule of a call ----------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <algorithm>
 #include "../../include/paradis_hip.h"
 
 #define WAVE 64
@@ -30,6 +31,12 @@ bool paradis_deterministic();
   } while (0)
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the address test of the 16-byte (float4 / LDS-DMA) paths; host, and the one kernel that tests its operands itself
+__host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// grid of a grid-stride streaming kernel with 256-thread workgroups (gbias.hip, elementwise.hip)
+inline int stream_blocks(int64_t n_items) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>((n_items + 255) / 256, 256 * 16));
+}
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property: a kernel family keeps one
 // of these and asks `first()` before its launches (true once per device of the calling process).

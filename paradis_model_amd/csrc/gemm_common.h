@@ -364,7 +364,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[2
           if (resb) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) t[q] = resb[base + ROWOFF(q)];
-            if (g.gate) {   // h + sigmoid(alpha) (adv - h): the arithmetic of gated_blend_fwd_kernel (misc.hip), bit for bit
+            if (g.gate) {   // h + sigmoid(alpha) (adv - h): the arithmetic of gated_blend_fwd_kernel (elementwise.hip), bit for bit
 #pragma unroll
               for (int q = 0; q < 8; ++q) {
                 const float gm = gate_sigmoid(g.gate[mrow + (q & 3) + 8 * (2 * h + (q >> 2))]);
@@ -871,8 +871,6 @@ constexpr size_t tall_lds_bytes() { return (size_t)2 * TALL_STAGE * 16; }
 constexpr int SQ_P = 256 + 8, SQ_STAGE = 4 * SQ_P;
 constexpr size_t sq_lds_bytes() { return (size_t)4 * SQ_STAGE * 16; }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---- the weight gradient's plan: dW[M,K] = sum_b dY[b][M,N] . X[b][K,N]^T ---------------------------------------------------
 // ONE place decides which kernel runs, how many K-range slabs it writes, its launch geometry, whether it fuses the bias
 // gradient's row sums and where slabs and row sums live in the workspace.  paradis_pw_gemm_wgrad launches from it,
@@ -960,7 +958,7 @@ inline size_t wgrad_ws_bytes(int B, int M, int K, int N, const GemmTunables& t) 
 struct SlabReduce { int64_t n; int vec, blocks1, n2, blocks2; };
 inline SlabReduce wgrad_reduce(const WgradPlan& p, const void* workspace, const void* dW, bool rowsums) {
   const int64_t n = p.to_slabs ? (int64_t)p.ws.M * p.ws.K : 0;
-  const int vec = n % 4 == 0 && ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(dW)) & 15) == 0;
+  const int vec = n % 4 == 0 && aligned16(workspace) && aligned16(dW);
   const int n2 = rowsums ? p.ws.M : 0;
   return {n, vec, n ? (int)std::min<int64_t>(((vec ? n / 4 : n) + 255) / 256, 2048) : 0, n2, (n2 + 255) / 256};
 }

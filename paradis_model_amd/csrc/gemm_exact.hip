@@ -120,10 +120,8 @@ pw_gemm_kernel(GemmArgs g) {
   const float* Ab = g.A + (g.inner > 0 ? 0 : (int64_t)bz * g.a_bs);
   const float* Bb = g.B + (g.inner > 0 ? 0 : (int64_t)bz * g.b_bs);
 
-  const bool a_vec = ((g.lda & 3) == 0) && ((reinterpret_cast<uintptr_t>(g.A) & 15) == 0) &&
-                     ((g.a_bs & 3) == 0) && ((g.a_is & 3) == 0);
-  const bool b_vec = ((g.ldb & 3) == 0) && ((reinterpret_cast<uintptr_t>(g.B) & 15) == 0) &&
-                     ((g.b_bs & 3) == 0) && ((g.b_is & 3) == 0);
+  const bool a_vec = ((g.lda & 3) == 0) && aligned16(g.A) && ((g.a_bs & 3) == 0) && ((g.a_is & 3) == 0);
+  const bool b_vec = ((g.ldb & 3) == 0) && aligned16(g.B) && ((g.b_bs & 3) == 0) && ((g.b_is & 3) == 0);
 
   // Co-resident workgroups of one CU (dispatch ids 256 apart) run the same program with one
   // barrier per k-tile and drift into lockstep: their non-MFMA phases (LDS store, barrier, global

@@ -487,7 +487,7 @@ int64_t split_image_chunks(int M, int K, int np = 3) {
 }
 
 int launch_amax(const float* x, int B, int64_t inner, int64_t bs, uint32_t* out, hipStream_t st) {
-  const int vec = (inner % 4 == 0) && (bs % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  const int vec = (inner % 4 == 0) && (bs % 4 == 0) && aligned16(x);
   hipLaunchKernelGGL(amax_partials_kernel, dim3(AMAX_WORDS), dim3(256), 0, st, x, B, inner, bs, vec, out);
   return 0;
 }

@@ -9,7 +9,7 @@
 // channel spread far below |m| does not forgive (x = 100 +- 0.01: xhat 4e-4 off, y and gx 1e-3 - the fp32 ATen module has
 // the same error).  The differences d = x - m are exact there, so the residual delta = sum_c d / C of the true mean is
 // formed from them and  xhat = (d - delta) rstd,  var = (sum d^2 - delta sum d) / (C-1)  (the shifted-data form of the
-// same two-pass definition).  Forward and the streaming backward both do; `mean` stays the fp32 mean.
+// same two-pass definition).  Forward and backward both do; `mean` stays the fp32 mean.
 #include <algorithm>
 #include "common.h"
 
@@ -225,278 +225,22 @@ channel_norm_fwd32_kernel(CatSrc s, const float* __restrict__ w, const float* __
   }
 }
 
-// gx = rstd * ( g*w - mean_c(g*w) - xhat * sum_c(g*w*xhat)/(C-1) )
-__global__ void __launch_bounds__(1024)
-channel_norm_bwd_dx_kernel(const float* __restrict__ gy, CatSrc s, const float* __restrict__ w,
-                           const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-                           float* __restrict__ gx1, float* __restrict__ gx2, int64_t gbs1,
-                           int64_t gbs2, const float* __restrict__ add1, int64_t abs1, int P, int tiles) {
-  __shared__ float red[2][16][NPX];
-  __shared__ float stat[2][NPX];
-  const int C = s.C1 + s.C2;
-  const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * NPX;
-  const int lane = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int p = p0 + lane;
-  const bool live = p < P;
-  const float mean = live ? mean_in[(int64_t)b * P + p] : 0.f;
-  const float rstd = live ? rstd_in[(int64_t)b * P + p] : 0.f;
-  const float* gyb = gy + (int64_t)b * C * P + p;
-  float s1 = 0.f, s2 = 0.f;
-  for (int c = grp; c < C; c += 16) {
-    if (live) {
-      const float gh = gyb[(int64_t)c * P] * w[c];
-      const float xh = (s.row(b, c, P)[p] - mean) * rstd;
-      s1 += gh;
-      s2 += gh * xh;
-    }
-  }
-  red[0][grp][lane] = s1;
-  red[1][grp][lane] = s2;
-  __syncthreads();
-  if (grp < 2) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += red[grp][k][lane];
-    stat[grp][lane] = t;
-  }
-  __syncthreads();
-  if (live) {
-    const float m1 = stat[0][lane] / (float)C, m2 = stat[1][lane] / (float)(C - 1);
-    for (int c = grp; c < C; c += 16) {
-      const float gh = gyb[(int64_t)c * P] * w[c];
-      const float xh = (s.row(b, c, P)[p] - mean) * rstd;
-      const float v = rstd * (gh - m1 - xh * m2);
-      if (c < s.C1) {
-        const float o = v + (add1 ? add1[(int64_t)b * abs1 + (int64_t)c * P + p] : 0.f);
-        gx1[(int64_t)b * gbs1 + (int64_t)c * P + p] = o;
-      } else if (gx2) gx2[(int64_t)b * gbs2 + (int64_t)(c - s.C1) * P + p] = v;
-    }
-  }
-}
-
-// gw[c] = sum_{b,p} gy * xhat ; gb[c] = sum_{b,p} gy.  grid (C, chunks): partial[c][chunk][2]
-__global__ void __launch_bounds__(256)
-channel_norm_bwd_dw_kernel(const float* __restrict__ gy, CatSrc s, const float* __restrict__ mean_in,
-                           const float* __restrict__ rstd_in, float* __restrict__ partial, int B,
-                           int P, int chunks) {
-  __shared__ float red[2][4];
-  const int C = s.C1 + s.C2;
-  const int c = blockIdx.x / chunks, chunk = blockIdx.x - c * chunks;
-  const int64_t total = (int64_t)B * P;
-  float aw = 0.f, ab = 0.f;
-  for (int64_t i = (int64_t)chunk * 256 + threadIdx.x; i < total; i += (int64_t)chunks * 256) {
-    const int b = (int)(i / P), p = (int)(i - (int64_t)b * P);
-    const float g = gy[((int64_t)b * C + c) * P + p];
-    const float xh = (s.row(b, c, P)[p] - mean_in[i]) * rstd_in[i];
-    aw += g * xh;
-    ab += g;
-  }
-  aw = wave_sum_dpp(aw);
-  ab = wave_sum_dpp(ab);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[0][wave] = aw; red[1][wave] = ab; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    const float t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-    partial[((int64_t)c * chunks + chunk) * 2 + threadIdx.x] = t;
-  }
-}
-
-__global__ void __launch_bounds__(256)
-channel_norm_bwd_finish(const float* __restrict__ partial, float* __restrict__ gw,
-                        float* __restrict__ gb, int C, int chunks) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  float a = 0.f, b = 0.f;
-  for (int k = 0; k < chunks; ++k) {
-    a += partial[((int64_t)c * chunks + k) * 2];
-    b += partial[((int64_t)c * chunks + k) * 2 + 1];
-  }
-  gw[c] = a;
-  gb[c] = b;
-}
-
-// Fused backward: one pass over (gy, x) produces the input gradient AND the per-channel partial sums
-// of the weight/bias gradients.  1024 threads = 32 pixels x 32 channel groups; a thread keeps its
-// <= MAXC gy values in registers and parks xhat in LDS (32 px x C floats <= 147 KiB of the 160 KiB),
-// so gy and x are read from HBM exactly once (the three-kernel path reads each twice and then once
-// more for the parameter gradients).
-// partial layout: [block][2][C]  (row 0: sum gy*xhat, row 1: sum gy) over the block's 32 pixels.
-template <int MAXC, int NPB>   // NPB pixels x 32 channel groups per workgroup (NPB = 32 or 16)
-__global__ void __launch_bounds__(NPB * 32)
-channel_norm_bwd_fused_kernel(const float* __restrict__ gy, CatSrc s, const float* __restrict__ w,
-                              const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-                              float* __restrict__ gx1, float* __restrict__ gx2, int64_t gbs1,
-                              int64_t gbs2, const float* __restrict__ add1, int64_t abs1, float* __restrict__ partial, int P, int tiles) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];   // [2][32][NPB] reduce + [C][NPB] xhat
-  float (*red)[32][NPB] = reinterpret_cast<float (*)[32][NPB]>(lds);
-  float* xs = lds + 2 * 32 * NPB;
-  const int C = s.C1 + s.C2;
-  const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * NPB;
-  const int px = threadIdx.x % NPB, grp = threadIdx.x / NPB;
-  const int p = p0 + px;
-  const bool live = p < P;
-  const float mean = live ? mean_in[(int64_t)b * P + p] : 0.f;
-  const float rstd = live ? rstd_in[(int64_t)b * P + p] : 0.f;
-  float g[MAXC];
-  float s1 = 0.f, s2 = 0.f;
-  // loads in batches from clamped (always valid) addresses, selected afterwards: a load under a
-  // per-lane condition is waited for on its own
-  const int pc = min(p, P - 1);
-  const float* gyc = gy + (int64_t)b * C * P + pc;
-  constexpr int CH = MAXC % 6 == 0 ? 6 : 4;
-#pragma unroll
-  for (int i0 = 0; i0 < MAXC; i0 += CH) {
-    float xv[CH];
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const int c = min(grp + 32 * (i0 + j), C - 1);
-      g[i0 + j] = gyc[(int64_t)c * P];
-      xv[j] = s.row(b, c, P)[pc];
-    }
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const int c = grp + 32 * (i0 + j);
-      const bool on = live && c < C;
-      g[i0 + j] = on ? g[i0 + j] : 0.f;
-      if (c < C) {
-        const float xh = on ? (xv[j] - mean) * rstd : 0.f;
-        xs[c * NPB + px] = xh;
-        const float gh = g[i0 + j] * w[c];
-        s1 += gh;
-        s2 += gh * xh;
-      }
-    }
-  }
-  red[0][grp][px] = s1;
-  red[1][grp][px] = s2;
-  __syncthreads();
-  if (grp < 2) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) t += red[grp][k][px];
-    red[grp][0][px] = t;
-  }
-  __syncthreads();
-  const float m1 = red[0][0][px] / (float)C, m2 = red[1][0][px] / (float)(C - 1);
-  float* pw = partial + (int64_t)blockIdx.x * 2 * C;
-#pragma unroll
-  for (int i = 0; i < MAXC; ++i) {
-    const int c = grp + 32 * i;
-    if (c < C) {
-      const float xh = xs[c * NPB + px];
-      if (live) {
-        const float v = rstd * (g[i] * w[c] - m1 - xh * m2);
-        if (c < s.C1) {
-          const float o = v + (add1 ? add1[(int64_t)b * abs1 + (int64_t)c * P + p] : 0.f);
-          gx1[(int64_t)b * gbs1 + (int64_t)c * P + p] = o;
-        } else if (gx2) gx2[(int64_t)b * gbs2 + (int64_t)(c - s.C1) * P + p] = v;
-      }
-      float a = g[i] * xh, d = g[i];       // dead pixels hold zeros
-#pragma unroll
-      for (int o = NPB / 2; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o, NPB);
-        d += __shfl_xor(d, o, NPB);
-      }
-      if (px == 0) { pw[c] = a; pw[C + c] = d; }
-    }
-  }
-}
-
-// Same work with nothing parked between the two phases: gy and x are streamed twice, the second time
-// a few microseconds after the first (the tile is 32 px x C x 8 B = 295 KiB: served by L2 / the
-// Infinity Cache, HBM traffic unchanged).  512 threads = 32 pixels x 16 channel groups, 4 KiB of LDS,
-// ~40 VGPRs: four workgroups share a CU, so loads, reductions and stores of different tiles overlap
-// (the register/LDS-resident version fits one workgroup per CU and runs its phases back to back).
-template <bool HAS_ADD>
-__global__ void __launch_bounds__(512)
-channel_norm_bwd_reread_kernel(const float* __restrict__ gy, CatSrc s, const float* __restrict__ w,
-                               const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
-                               float* __restrict__ gx1, float* __restrict__ gx2, int64_t gbs1,
-                               int64_t gbs2, const float* __restrict__ add1, int64_t abs1, float* __restrict__ partial, int P, int tiles) {
-  constexpr int NPB = 32, G = 16;
-  __shared__ float red[2][G][NPB];
-  const int C = s.C1 + s.C2;
-  const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * NPB;
-  const int px = threadIdx.x % NPB, grp = threadIdx.x / NPB;
-  const int p = min(p0 + px, P - 1);          // clamped: loads are unconditional, stores predicated
-  const bool live = p0 + px < P;
-  const float mean = mean_in[(int64_t)b * P + p];
-  const float rstd = rstd_in[(int64_t)b * P + p];
-  const float* gyb = gy + (int64_t)b * C * P + p;
-  float s1 = 0.f, s2 = 0.f;
-  constexpr int U = 6;   // channels per batch: 2*U loads in flight per thread, issued before their use
-  for (int c0 = grp; c0 < C; c0 += G * U) {
-    float gv[U], xv[U], wv[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int c = min(c0 + G * j, C - 1);
-      gv[j] = gyb[(int64_t)c * P];
-      xv[j] = s.row(b, c, P)[p];
-      wv[j] = c0 + G * j < C ? w[c] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const float gh = gv[j] * wv[j];
-      s1 += gh;
-      s2 += gh * ((xv[j] - mean) * rstd);
-    }
-  }
-  red[0][grp][px] = live ? s1 : 0.f;
-  red[1][grp][px] = live ? s2 : 0.f;
-  __syncthreads();
-  if (grp < 2) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < G; ++k) t += red[grp][k][px];
-    red[grp][0][px] = t;
-  }
-  __syncthreads();
-  const float m1 = red[0][0][px] / (float)C, m2 = red[1][0][px] / (float)(C - 1);
-  float* pw = partial + (int64_t)blockIdx.x * 2 * C;
-  for (int c0 = grp; c0 < C; c0 += G * U) {
-    float gv[U], xv[U], wv[U], av[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int c = min(c0 + G * j, C - 1);
-      gv[j] = gyb[(int64_t)c * P];
-      xv[j] = s.row(b, c, P)[p];
-      wv[j] = w[c];
-      av[j] = HAS_ADD ? add1[(int64_t)b * abs1 + (int64_t)min(c, s.C1 - 1) * P + p] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int c = c0 + G * j;
-      if (c < C) {
-        const float g = live ? gv[j] : 0.f;     // dead pixels contribute zeros
-        const float xh = (xv[j] - mean) * rstd;
-        if (live) {
-          const float v = rstd * (g * wv[j] - m1 - xh * m2);
-          if (c < s.C1) {
-            gx1[(int64_t)b * gbs1 + (int64_t)c * P + p] = v + av[j];
-          } else if (gx2) gx2[(int64_t)b * gbs2 + (int64_t)(c - s.C1) * P + p] = v;
-        }
-        float a = g * xh, d = g;
-#pragma unroll
-        for (int o = NPB / 2; o > 0; o >>= 1) {
-          a += __shfl_xor(a, o, NPB);
-          d += __shfl_xor(d, o, NPB);
-        }
-        if (px == 0) { pw[c] = a; pw[C + c] = d; }
-      }
-    }
-  }
-}
-
-// ---- backward as two STREAMING kernels (round 3) ------------------------------------------------------------
-// The fused kernels above move 128-byte row segments (32 pixels x 4 B per channel row) because a workgroup must see
-// all C channels of its pixels: 3.4 TB/s forward, and the backward's second read of (gy, x) misses the caches in the
-// training step (256 KiB per workgroup x 1024 resident workgroups).  Split by WHAT IS REDUCED instead:
+// ---- backward: two STREAMING kernels and a fixed-order finish ------------------------------------------------------------
+// A workgroup that owns all C channels of its pixels moves 128-byte row segments (32 pixels x 4 B per channel row) and,
+// to form gx, needs (gy, x) a second time.  Split by WHAT IS REDUCED instead:
 //   stats : m1[b,p] = sum_c gy w / C,  m2[b,p] = sum_c gy w xhat / (C-1): lanes along the pixel axis (256-byte row
 //           segments per wave), the four waves of a workgroup take channels g, g+4, ...; reads gy and x once;
 //   apply : gx = rstd (gy w - m1 - xhat m2) (+ addend), one workgroup per (sample, channel) row, 16-byte accesses,
 //           and - the row being one channel - the parameter-gradient sums of that row fall out of the same pass.
-// Same HBM bytes as the reread kernel (gy and x twice), all of them at streaming efficiency; deterministic.
+// gy and x are read twice, all of it at streaming efficiency; deterministic.  This is the only backward: a shape whose
+// apply grid does not fit 31 bits (a cotangent of 8 GiB or more) is refused, see norm_bwd_plan.
+// Retired (code in git, measurements in DESIGN_HISTORY.md section 4.4 and profiles/history/): round 1's dx / dw / finish chain (gy and
+// x twice, then once more for the parameter gradients); round 2's one-pass kernel with gy in registers and xhat parked
+// in 147 KiB of LDS (one workgroup per CU, phases back to back: 423 us isolated, 392 us in the step; 16-pixel tiles 587
+// us) and its stream-twice successor (four workgroups per CU: 331 us isolated, 356 us in the step with the addend -
+// its second read of 256 KiB per workgroup missed every cache; step 231.6 against 235.2 ms).  Against that successor
+// the pair below: 407 -> 316 us at 32 x 64, B = 32, C = 1024 with the addend, step 162.7 -> 160.6 ms.  Both centred
+// on the fp32 mean alone, not on the corrected mean of the file header.
 // GY16 (round 6, bf16-mixed mode): the cotangent is a bf16 tensor - the data gradient of the pointwise GEMM that consumed a
 // bf16-stored y, bf16-valued in the reference's autocast backward as well (the gradient of conv2d's bf16 input).
 constexpr int NSTAT_PX = 64, NSTAT_G = 4, NSTAT_U = 8;
@@ -659,29 +403,49 @@ channel_norm_bwd_fused_finish2(const float* __restrict__ chunk, float* __restric
   gb[c] = (float)d;
 }
 
-int dw_chunks(int B, int C, int P) {
-  const int64_t total = (int64_t)B * P;
-  int chunks = (2048 + C - 1) / C;
-  chunks = (int)std::min<int64_t>(chunks, (total + 255) / 256);
-  return std::max(chunks, 1);
+// nullptr, or what is wrong with the shape (both directions; C2 = 0 for a query that knows only C)
+const char* norm_shape_error(int B, int C1, int C2, int P) {
+  if (!(B >= 0 && C1 >= 1 && C2 >= 0 && P >= 1)) return "bad shape";
+  if (C1 + C2 < 2) return "needs at least two channels (unbiased variance)";
+  if ((int64_t)B * ((P + 31) / 32) >= (1ll << 31)) return "too large";
+  return nullptr;
 }
-
-int g_norm_fwd_px = 32;   // pixels per forward workgroup (32 or 64); diagnostic knob
-int g_norm_bwd_reread = 1;  // backward: re-read x through L2 (two workgroups per CU) vs xhat parked in LDS
-
 int check_norm(const char* name, int B, int C1, int C2, int P) {
-  PD_REQUIRE(B >= 0 && C1 >= 1 && C2 >= 0 && P >= 1, "%s: bad shape", name);
-  PD_REQUIRE(C1 + C2 >= 2, "%s: needs at least two channels (unbiased variance)", name);
-  PD_REQUIRE((int64_t)B * ((P + 31) / 32) < (1ll << 31), "%s: too large", name);
+  const char* e = norm_shape_error(B, C1, C2, P);
+  PD_REQUIRE(e == nullptr, "%s: %s", name, e);
   return 0;
 }
 
-}  // namespace
+// ---- the backward's plan ------------------------------------------------------------------------------------------------------
+// ONE place holds the launch geometry of the four kernels and where their intermediates live in the workspace:
+// paradis_channel_norm_bwd launches from it, paradis_channel_norm_bwd_ws_bytes and _bwd16_ok ask it.  Host only.
+constexpr int APPLY_SPAN = 8192;   // pixels per workgroup of the apply kernel (one (sample, channel) row chunk); multiple of 4
+constexpr int FINISH_ROWS = 64;    // rows of `partial` that one workgroup row of the first finish stage sums
+struct NormBwdPlan {
+  bool fits;           // the apply grid B * C * apply_chunks fits 31 bits (the stats grid does by check_norm); the counts
+                       // below mean something only then
+  int stats_tiles;     // NSTAT_PX-pixel tiles per sample: stats grid = B * stats_tiles
+  int apply_chunks;    // APPLY_SPAN-pixel chunks per row: apply grid = B * C * apply_chunks
+  int nblk;            // B * apply_chunks rows of partial[nblk][2][C]
+  int finish_chunks;   // ceil(nblk / FINISH_ROWS) rows of chunk[finish_chunks][2][C]
+  size_t m1, m2, dl, partial, chunk, total;   // element offsets into the fp32 workspace, and its size in elements
+};
+NormBwdPlan norm_bwd_plan(int B, int C, int P) {
+  const int64_t chunks = ((int64_t)P + APPLY_SPAN - 1) / APPLY_SPAN, nblk = B * chunks, fin = (nblk + FINISH_ROWS - 1) / FINISH_ROWS;
+  const size_t bp = (size_t)B * P, row = (size_t)2 * C;
+  NormBwdPlan p;
+  p.fits = nblk * C < (1ll << 31);
+  p.stats_tiles = (P + NSTAT_PX - 1) / NSTAT_PX;
+  p.apply_chunks = (int)chunks;
+  p.nblk = (int)nblk;
+  p.finish_chunks = (int)fin;
+  p.m1 = 0, p.m2 = bp, p.dl = 2 * bp, p.partial = 3 * bp;
+  p.chunk = p.partial + (size_t)nblk * row;
+  p.total = p.chunk + (size_t)fin * row;
+  return p;
+}
 
-#ifdef PARADIS_DEV_KNOBS   // development build only (`make dev`, tools/stencil_bench.py)
-extern "C" void paradis_debug_set_norm_fwd_px(int px) { g_norm_fwd_px = px == 64 ? 64 : 32; }
-extern "C" void paradis_debug_set_norm_bwd_reread(int on) { g_norm_bwd_reread = on ? 1 : 0; }
-#endif
+}  // namespace
 
 #ifndef NORM_FWD32      // (A/B builds: 0 = the generic 32-pixel kernel)
 #define NORM_FWD32 1
@@ -697,7 +461,7 @@ static int channel_norm_fwd_impl(const float* x1, const float* x2, const float* 
   const int C = C1 + C2;
   hipStream_t st = (hipStream_t)stream;
   const dim3 block(1024);
-  if (C <= 32 * 36 && g_norm_fwd_px == 32) {          // 32 pixels x 32 groups, two workgroups per CU
+  if (C <= 32 * 36) {          // 32 pixels x 32 groups, two workgroups per CU
     const int tiles = (P + 31) / 32;
     const dim3 grid((unsigned)((int64_t)B * tiles));
     if (C <= 32 * 4)
@@ -706,15 +470,10 @@ static int channel_norm_fwd_impl(const float* x1, const float* x2, const float* 
       hipLaunchKernelGGL((channel_norm_fwd32_kernel<36, Y16>), grid, block, 0, st, s, w, b, y, mean, rstd, P, tiles, eps);
     else
       hipLaunchKernelGGL((channel_norm_fwd_kernel<36, 32, Y16>), grid, block, 0, st, s, w, b, y, mean, rstd, P, tiles, eps);
-  } else {
+  } else {                     // any C: three passes over 64-pixel tiles
     const int tiles = (P + NPX - 1) / NPX;
     const dim3 grid((unsigned)((int64_t)B * tiles));
-    if (C <= 16 * 8)
-      hipLaunchKernelGGL((channel_norm_fwd_kernel<8, NPX, Y16>), grid, block, 0, st, s, w, b, y, mean, rstd, P, tiles, eps);
-    else if (C <= 16 * 72)
-      hipLaunchKernelGGL((channel_norm_fwd_kernel<72, NPX, Y16>), grid, block, 0, st, s, w, b, y, mean, rstd, P, tiles, eps);
-    else
-      hipLaunchKernelGGL((channel_norm_fwd_kernel<0, NPX, Y16>), grid, block, 0, st, s, w, b, y, mean, rstd, P, tiles, eps);
+    hipLaunchKernelGGL((channel_norm_fwd_kernel<0, NPX, Y16>), grid, block, 0, st, s, w, b, y, mean, rstd, P, tiles, eps);
   }
   PD_CHECK_LAUNCH("channel_norm_fwd");
   return 0;
@@ -733,26 +492,8 @@ extern "C" int paradis_channel_norm_fwd16(const float* x1, const float* x2, cons
   return channel_norm_fwd_impl<true>(x1, x2, w, b, (float*)y, mean, rstd, B, C1, C2, P, x1_bs, x2_bs, eps, stream);
 }
 
-// pixels per workgroup of the apply kernel (one (sample, channel) row chunk); multiple of 4
-constexpr int APPLY_SPAN = 8192;
-#ifndef NORM_BWD_STREAMING    // (A/B builds: 0 = the fused reread kernel of round 2)
-#define NORM_BWD_STREAMING 1
-#endif
-
 extern "C" size_t paradis_channel_norm_bwd_ws_bytes(int B, int C, int P) {
-  const size_t b = (size_t)std::max(B, 1);
-  const size_t three_kernel = (size_t)C * dw_chunks((int)b, C, P) * 2 * sizeof(float);
-  const size_t nblk = b * ((P + 31) / 32);
-  const size_t fused = (nblk + (nblk + 63) / 64) * 2 * C * sizeof(float);   // per-block partials + per-chunk sums
-  const size_t nrow = b * ((P + APPLY_SPAN - 1) / APPLY_SPAN);
-  const size_t streaming = (3 * b * P + (nrow + (nrow + 63) / 64) * 2 * C) * sizeof(float);
-  return std::max({three_kernel, fused, streaming}) + 256;
-}
-
-// shapes whose backward runs as the two streaming kernels (the only ones with a bf16-cotangent instantiation)
-static bool norm_bwd_streaming(int B, int C, int P) {
-  const int apply_chunks = (P + APPLY_SPAN - 1) / APPLY_SPAN;
-  return NORM_BWD_STREAMING && (int64_t)B * C * apply_chunks < (1ll << 31) && (int64_t)B * ((P + 63) / 64) < (1ll << 31);
+  return norm_bwd_plan(std::max(B, 1), C, P).total * sizeof(float) + 256;
 }
 
 template <bool GY16>
@@ -763,8 +504,11 @@ static int channel_norm_bwd_impl(const float* gy, const float* x1, const float* 
                                  int64_t gx2_bs, const float* addend1, int64_t add1_bs,
                                  void* workspace, void* stream) {
   if (int e = check_norm("channel_norm_bwd", B, C1, C2, P)) return e;
-  PD_REQUIRE(workspace != nullptr, "channel_norm_bwd: workspace required");
   const int C = C1 + C2;
+  const NormBwdPlan pl = norm_bwd_plan(B, C, P);
+  PD_REQUIRE(pl.fits, "channel_norm_bwd: too large (B = %d, C = %d, P = %d: B * C * ceil(P / %d) must stay below 2^31)", B, C, P,
+             APPLY_SPAN);
+  PD_REQUIRE(workspace != nullptr, "channel_norm_bwd: workspace required");
   hipStream_t st = (hipStream_t)stream;
   if (B == 0) {
     if (pd_zero_async(gw, C * sizeof(float), st) != hipSuccess ||
@@ -775,100 +519,33 @@ static int channel_norm_bwd_impl(const float* gy, const float* x1, const float* 
     return 0;
   }
   CatSrc s{x1, x2, C1, C2, x1_bs, x2_bs};
-  int nblk = 0;
-  const int apply_chunks = (P + APPLY_SPAN - 1) / APPLY_SPAN;
-  if (norm_bwd_streaming(B, C, P)) {
-    float* m1 = (float*)workspace;
-    float* m2 = m1 + (size_t)B * P;
-    float* dl = m2 + (size_t)B * P;
-    float* partial = dl + (size_t)B * P;
-    const int tiles = (P + NSTAT_PX - 1) / NSTAT_PX;
-    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = P % 4 == 0 && x1_bs % 4 == 0 && (C2 == 0 || (x2_bs % 4 == 0 && a16(x2))) && gx1_bs % 4 == 0 &&
-                     (gx2 == nullptr || (gx2_bs % 4 == 0 && a16(gx2))) && (addend1 == nullptr || (add1_bs % 4 == 0 && a16(addend1))) &&
-                     a16(gy) && a16(x1) && a16(gx1) && a16(mean) && a16(rstd) && a16(workspace) && ((size_t)B * P) % 4 == 0;
-    // (Round 6: the two passes over chunks of the batch, stats then apply, so that the apply pass would find the gy / x it
-    //  re-reads in the 256 MB memory-side cache - every index is per sample, a chunk is the same launch on offset pointers.
-    //  Measured, removed: 318 us per call in one chunk, 371 / 424 / 600 / 1338 us with read sets of 160 / 96 / 48 / 24 MB per
-    //  chunk at 32 x 64, B = 32, C = 1024; the training step 152.7 -> 156.5 / 163.8 ms.  profiles/r06_norm_bwd_chunked.txt)
-    hipLaunchKernelGGL(channel_norm_bwd_stats_kernel<GY16>, dim3((unsigned)((int64_t)B * tiles)), dim3(NSTAT_PX * NSTAT_G), 0,
-                       st, gy, s, w, mean, rstd, m1, m2, dl, P, tiles);
-    const unsigned grid = (unsigned)((int64_t)B * C * apply_chunks);
-    if (vec)
-      hipLaunchKernelGGL((channel_norm_bwd_apply_kernel<true, GY16>), dim3(grid), dim3(256), 0, st, gy, s, w, mean, rstd,
-                         (const float*)m1, (const float*)m2, (const float*)dl, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
-                         APPLY_SPAN, apply_chunks);
-    else
-      hipLaunchKernelGGL((channel_norm_bwd_apply_kernel<false, GY16>), dim3(grid), dim3(256), 0, st, gy, s, w, mean, rstd,
-                         (const float*)m1, (const float*)m2, (const float*)dl, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
-                         APPLY_SPAN, apply_chunks);
-    nblk = B * apply_chunks;
-    const int rows = 64, chunks = (nblk + rows - 1) / rows;
-    float* chunk = partial + (size_t)nblk * 2 * C;
-    hipLaunchKernelGGL(channel_norm_bwd_fused_finish, dim3((C + 255) / 256, chunks), dim3(256), 0, st,
-                       (const float*)partial, chunk, C, nblk, rows);
-    hipLaunchKernelGGL(channel_norm_bwd_fused_finish2, dim3((C + 255) / 256), dim3(256), 0, st, (const float*)chunk, gw,
-                       gb, C, chunks);
-    PD_CHECK_LAUNCH("channel_norm_bwd(streaming)");
-    return 0;
-  }
-  if constexpr (GY16) {
-    paradis_set_error("channel_norm_bwd16: shape outside the streaming kernels (paradis_channel_norm_bwd16_ok)");
-    return 1;
-  } else {
-  // (the kernels below - A/B builds with NORM_BWD_STREAMING = 0 - centre on the fp32 mean alone: file header)
-  if (C <= 32 * 36 && (int64_t)B * ((P + 31) / 32) < (1ll << 31)) {
-    // g_norm_bwd_reread: 1 = stream-twice kernel (default; in the training step 231.6 vs 235.2 ms),
-    // 0 = gy in registers + xhat in LDS, one workgroup per CU (half the HBM traffic, phases serialised).
-    // (16-pixel tiles of the resident kernel, two workgroups per CU: 587 vs 365 us - not kept.)
-    const int NPBr = 32;
-    const int tiles32 = (P + NPBr - 1) / NPBr;
-    nblk = B * tiles32;
-    float* partial = (float*)workspace;
-    const size_t lds = (size_t)(2 * 32 * NPBr + C * NPBr) * sizeof(float);
-    static PerDeviceOnce once;
-    if (once.first()) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&channel_norm_bwd_fused_kernel<36, 32>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&channel_norm_bwd_fused_kernel<4, 32>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        paradis_set_error("channel_norm_bwd: cannot reserve LDS");
-        return 2;
-      }
-    }
-    if (g_norm_bwd_reread == 1 && addend1)
-      hipLaunchKernelGGL(channel_norm_bwd_reread_kernel<true>, dim3(nblk), dim3(512), 0, st, gy, s, w, mean,
-                         rstd, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P, tiles32);
-    else if (g_norm_bwd_reread == 1)
-      hipLaunchKernelGGL(channel_norm_bwd_reread_kernel<false>, dim3(nblk), dim3(512), 0, st, gy, s, w, mean,
-                         rstd, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P, tiles32);
-    else if (C <= 32 * 4)
-      hipLaunchKernelGGL((channel_norm_bwd_fused_kernel<4, 32>), dim3(nblk), dim3(32 * 32), lds, st, gy, s,
-                         w, mean, rstd, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P, tiles32);
-    else
-      hipLaunchKernelGGL((channel_norm_bwd_fused_kernel<36, 32>), dim3(nblk), dim3(32 * 32), lds, st, gy, s,
-                         w, mean, rstd, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P, tiles32);
-    const int rows = 64, chunks = (nblk + rows - 1) / rows;
-    float* chunk = partial + (size_t)nblk * 2 * C;
-    hipLaunchKernelGGL(channel_norm_bwd_fused_finish, dim3((C + 255) / 256, chunks), dim3(256), 0, st, partial,
-                       chunk, C, nblk, rows);
-    hipLaunchKernelGGL(channel_norm_bwd_fused_finish2, dim3((C + 255) / 256), dim3(256), 0, st, chunk, gw, gb, C,
-                       chunks);
-    PD_CHECK_LAUNCH("channel_norm_bwd(fused)");
-    return 0;
-  }
-  const int tiles = (P + NPX - 1) / NPX;
-  hipLaunchKernelGGL(channel_norm_bwd_dx_kernel, dim3((unsigned)((int64_t)B * tiles)), dim3(1024), 0, st,
-                     gy, s, w, mean, rstd, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, P, tiles);
-  const int chunks = dw_chunks(B, C, P);
-  float* partial = (float*)workspace;
-  hipLaunchKernelGGL(channel_norm_bwd_dw_kernel, dim3(C * chunks), dim3(256), 0, st, gy, s, mean, rstd,
-                     partial, B, P, chunks);
-  hipLaunchKernelGGL(channel_norm_bwd_finish, dim3((C + 255) / 256), dim3(256), 0, st, partial, gw, gb, C,
-                     chunks);
-  PD_CHECK_LAUNCH("channel_norm_bwd");
+  float* ws = (float*)workspace;
+  float *m1 = ws + pl.m1, *m2 = ws + pl.m2, *dl = ws + pl.dl, *partial = ws + pl.partial, *chunk = ws + pl.chunk;
+  const bool vec = P % 4 == 0 && x1_bs % 4 == 0 && (C2 == 0 || (x2_bs % 4 == 0 && aligned16(x2))) && gx1_bs % 4 == 0 &&
+                   (gx2 == nullptr || (gx2_bs % 4 == 0 && aligned16(gx2))) &&
+                   (addend1 == nullptr || (add1_bs % 4 == 0 && aligned16(addend1))) && aligned16(gy) && aligned16(x1) &&
+                   aligned16(gx1) && aligned16(mean) && aligned16(rstd) && aligned16(workspace) && ((size_t)B * P) % 4 == 0;
+  // (Round 6: the two passes over chunks of the batch, stats then apply, so that the apply pass would find the gy / x it
+  //  re-reads in the 256 MB memory-side cache - every index is per sample, a chunk is the same launch on offset pointers.
+  //  Measured, removed: 318 us per call in one chunk, 371 / 424 / 600 / 1338 us with read sets of 160 / 96 / 48 / 24 MB per
+  //  chunk at 32 x 64, B = 32, C = 1024; the training step 152.7 -> 156.5 / 163.8 ms.  profiles/r06_norm_bwd_chunked.txt)
+  hipLaunchKernelGGL(channel_norm_bwd_stats_kernel<GY16>, dim3((unsigned)((int64_t)B * pl.stats_tiles)), dim3(NSTAT_PX * NSTAT_G), 0,
+                     st, gy, s, w, mean, rstd, m1, m2, dl, P, pl.stats_tiles);
+  const unsigned grid = (unsigned)((int64_t)pl.nblk * C);
+  if (vec)
+    hipLaunchKernelGGL((channel_norm_bwd_apply_kernel<true, GY16>), dim3(grid), dim3(256), 0, st, gy, s, w, mean, rstd,
+                       (const float*)m1, (const float*)m2, (const float*)dl, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
+                       APPLY_SPAN, pl.apply_chunks);
+  else
+    hipLaunchKernelGGL((channel_norm_bwd_apply_kernel<false, GY16>), dim3(grid), dim3(256), 0, st, gy, s, w, mean, rstd,
+                       (const float*)m1, (const float*)m2, (const float*)dl, gx1, gx2, gx1_bs, gx2_bs, addend1, add1_bs, partial, P,
+                       APPLY_SPAN, pl.apply_chunks);
+  hipLaunchKernelGGL(channel_norm_bwd_fused_finish, dim3((C + 255) / 256, pl.finish_chunks), dim3(256), 0, st,
+                     (const float*)partial, chunk, C, pl.nblk, FINISH_ROWS);
+  hipLaunchKernelGGL(channel_norm_bwd_fused_finish2, dim3((C + 255) / 256), dim3(256), 0, st, (const float*)chunk, gw,
+                     gb, C, pl.finish_chunks);
+  PD_CHECK_LAUNCH("channel_norm_bwd(streaming)");
   return 0;
-  }
 }
 
 extern "C" int paradis_channel_norm_bwd(const float* gy, const float* x1, const float* x2,
@@ -881,9 +558,11 @@ extern "C" int paradis_channel_norm_bwd(const float* gy, const float* x1, const 
                                       addend1, add1_bs, workspace, stream);
 }
 
-// gy as a bf16 tensor [B][C1 + C2, P] (ABI 9; bf16-mixed mode); everything else as paradis_channel_norm_bwd.  Only where
-// paradis_channel_norm_bwd16_ok says so (the caller widens gy otherwise).
-extern "C" int paradis_channel_norm_bwd16_ok(int B, int C, int P) { return norm_bwd_streaming(std::max(B, 1), C, P) ? 1 : 0; }
+// gy as a bf16 tensor [B][C1 + C2, P] (ABI 9; bf16-mixed mode); everything else as paradis_channel_norm_bwd.
+// paradis_channel_norm_bwd16_ok: 1 exactly for the shapes that both entry points accept (C = C1 + C2).
+extern "C" int paradis_channel_norm_bwd16_ok(int B, int C, int P) {
+  return norm_shape_error(B, C, 0, P) == nullptr && norm_bwd_plan(B, C, P).fits ? 1 : 0;
+}
 extern "C" int paradis_channel_norm_bwd16(const void* gy, const float* x1, const float* x2,
                                           const float* w, const float* mean, const float* rstd,
                                           float* gx1, float* gx2, float* gw, float* gb, int B, int C1,

@@ -59,6 +59,31 @@ def test_argument_validation_without_gpu():
     assert L.paradis_sl_advect_ws_bytes(2, 3, 8, 16, 0) >= 2 * 3 * 4 * 4
 
 
+def test_channel_norm_backward_refuses_what_its_grid_cannot_hold():
+    """The backward has one schedule; its apply grid is B * C * ceil(P / 8192) workgroups and has to stay below 2^31.  A
+    larger shape is an error (it used to fall to kernels with another rounding), from both entry points' common check,
+    and paradis_channel_norm_bwd16_ok says 1 exactly where the call is accepted.  Nothing is launched."""
+    import ctypes
+    from paradis_model_amd import _lib
+    L = _lib.lib
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.c_void_p(ctypes.addressof(buf))      # (never dereferenced: the check fires before anything is touched)
+
+    def bwd(B, C1, C2, P):
+        return L.paradis_channel_norm_bwd(p, p, None, p, p, p, p, None, p, p, B, C1, C2, P, C1 * P, 0, C1 * P, 0, None, 0, p, None)
+
+    assert bwd(1 << 20, 1 << 11, 0, 1) == 1
+    msg = _lib.last_error()
+    assert "too large" in msg and str(1 << 20) in msg and str(1 << 11) in msg, msg
+    assert L.paradis_channel_norm_bwd16_ok(1 << 20, 1 << 11, 1) == 0
+    assert L.paradis_channel_norm_bwd16_ok((1 << 20) - 1, 1 << 11, 1) == 1       # one row below the limit
+    assert L.paradis_channel_norm_bwd16_ok(32, 1152, 2048) == 1
+    assert L.paradis_channel_norm_bwd16_ok(32, 1, 2048) == 0                      # a shape the entry point rejects outright
+    # the streaming layout: m1, m2, dl [B, P], partial [B * chunks][2][C], chunk [ceil(B * chunks / 64)][2][C], 256 bytes of slack
+    assert L.paradis_channel_norm_bwd_ws_bytes(32, 1152, 2048) == (3 * 32 * 2048 + (32 + 1) * 2 * 1152) * 4 + 256
+    assert L.paradis_channel_norm_bwd_ws_bytes(0, 20, 100) == L.paradis_channel_norm_bwd_ws_bytes(1, 20, 100)
+
+
 # paradis_sl_advect_ws_bytes(B, K, H, W, flags) as the library of the commit before the advection unit was split
 # returned it (the layout did not change with the split: callers and saved workspaces depend on these totals)
 _S, _G, _TILED, _TILES = 4, 1, 2, 8      # PARADIS_ADVECT_SEPARABLE, _GENERIC, _TILED, _TILES (include/paradis_hip.h)

@@ -1,5 +1,5 @@
 """The small streaming / reduction kernels against plain fp64 references (tests/_refs64.py) at every dispatch edge:
-the shapes, alignments and sizes at which csrc/resample.hip, misc.hip, norm.hip and train.hip pick another kernel,
+the shapes, alignments and sizes at which csrc/resample.hip, gbias.hip, elementwise.hip, norm.hip and train.hip pick another kernel,
 another chunk count or another tail loop.  The parameter lists are derived from the dispatch conditions in the source;
 the comment next to a case names the branch it selects.
 
@@ -367,15 +367,21 @@ NORM_P = [8192,               # one chunk, exactly full
 NORM_CASES = [(20, 0, P, add, False) for P in NORM_P for add in (False, True)]
 NORM_CASES += [(1024, 128, P, i % 2 == 0, False) for i, P in enumerate(NORM_P)]     # the reaction block's virtual concat
 NORM_CASES += [(20, 0, 8196, False, True), (20, 0, 16387, True, True)]              # channel mean >> channel spread
+NORM_CASES = [pytest.param(3 if c[0] == 20 else 1, *c, id="-".join(map(str, c))) for c in NORM_CASES]
+# the parameter gradients' two-level reduction (norm_bwd_plan: FINISH_ROWS = 64 rows of `partial` per finish chunk, one row
+# per (sample, apply chunk)) with more than one finish chunk: B * ceil(P / 8192) > 64
+NORM_CASES += [pytest.param(65, 20, 0, 100, False, False, id="B65-20-0-100-False-False"),     # float4, two chunks, the second holds ONE row
+               pytest.param(130, 6, 0, 7, False, False, id="B130-6-0-7-False-False"),        # scalar, three chunks (64, 64, 2), ragged stats tile
+               pytest.param(65, 20, 12, 100, True, False, id="B65-20-12-100-True-False")]     # virtual concat, with addend
 
 
-@pytest.mark.parametrize("C1,C2,P,add,badly_conditioned", NORM_CASES)
-def test_channel_norm_backward(ops, record_property, C1, C2, P, add, badly_conditioned):
+@pytest.mark.parametrize("B,C1,C2,P,add,badly_conditioned", NORM_CASES)
+def test_channel_norm_backward(ops, record_property, B, C1, C2, P, add, badly_conditioned):
     """``badly_conditioned``: x = 100 + 0.01 randn per pixel, so x - mean cancels four of fp32's seven digits.  Centred on
     the fp32 mean alone (the reference module's arithmetic, and the kernels' until this test) every fp32 evaluation is
     1e-3 off there: y 9.2e-4, gx 3.6e-4, gw 1.5e-3 from the kernels against 9.7e-4, 2.4e-4, 1.1e-3 from the CPU oracle.
     The kernels now carry the mean's rounding residual (csrc/norm.hip, file header): 2.0e-7, 1.0e-7, 1.2e-7."""
-    B, C = (3 if C1 == 20 else 1), C1 + C2
+    C = C1 + C2
     positive = P % 2 == 1
     if badly_conditioned:
         x = 100.0 + 0.01 * _rand(1, B, C, 1, P)
@@ -386,8 +392,10 @@ def test_channel_norm_backward(ops, record_property, C1, C2, P, add, badly_condi
     gy = _rand(4, B, C, 1, P, positive=positive)
     _spike(gy, 3, [0, -1, 8191, 8192, 16383, 16384, 63, 64])       # ends of the row, of the apply chunks, of a stats tile
     _spike_cross(gy, 1, [0, -1, C1 - 1, C1], 3, [5, -7])           # ends of the sums over channels (m1, m2), at two pixels
+    if B > 64:                                                     # ends of the finish chunks (64 samples each), at two pixels
+        _spike_cross(gy, 0, [0, -1, 63, 64, 127, 128], 3, [2, -3])
     ct = _rand(5, B, C1, 1, P) if add else None
-    J = _Judge(record_property, f"norm bwd C{C1}+{C2} P{P} add{int(add)} cond{int(badly_conditioned)}")
+    J = _Judge(record_property, f"norm bwd B{B} C{C1}+{C2} P{P} add{int(add)} cond{int(badly_conditioned)}")
 
     def run(fn32, leaves):
         xs = leaves[0] if C2 == 0 else torch.cat(leaves[:2], 1)
@@ -426,8 +434,40 @@ def test_channel_norm_backward(ops, record_property, C1, C2, P, add, badly_condi
     J.done()
 
 
+# (B, C1, C2, P, addend): three apply chunks' worth of partial rows; the reaction block's concat, scalar path; two finish chunks
+NORM_WS_CASES = [(3, 20, 0, 8196, False), (1, 1024, 128, 8191, True), (65, 20, 0, 100, False)]
+
+
+@pytest.mark.parametrize("B,C1,C2,P,add", NORM_WS_CASES)
+def test_channel_norm_backward_workspace(ops, L, B, C1, C2, P, add):
+    """paradis_channel_norm_bwd_ws_bytes is what norm_bwd_plan lays out and no more: a call through the C ABI on a workspace
+    of exactly that size leaves the 4096 canary bytes behind it alone, and returns the bytes of the op (which sizes its own
+    workspace from the same query)."""
+    C = C1 + C2
+    x = _rand(1, B, C, 1, P, scale=3.0) + 1.0
+    x1, x2 = x[:, :C1].contiguous(), (x[:, C1:].contiguous() if C2 else None)
+    w, b = 1.0 + _rand(2, C, scale=0.2), _rand(3, C, scale=0.2)
+    gy = _rand(4, B, C, 1, P)
+    ct = _rand(5, B, C1, 1, P) if add else None
+    _, mean, rstd = ops._channel_norm(x1, x2, w, b, 1e-5)
+    want = ops._channel_norm_backward(gy, x1, x2, w, mean, rstd, ct)
+    nbytes = L.lib.paradis_channel_norm_bwd_ws_bytes(B, C, P)
+    ws = torch.full((nbytes + 4096,), 0xA5, dtype=torch.uint8, device="cuda")
+    assert ws.data_ptr() % 16 == 0
+    got = [torch.full_like(t, -7.0) for t in want]
+    rc = L.lib.paradis_channel_norm_bwd(L.dptr(gy), L.dptr(x1), L.dptr(x2), L.dptr(w), L.dptr(mean), L.dptr(rstd),
+                                        L.dptr(got[0]), L.dptr(got[1]) if C2 else None, L.dptr(got[2]), L.dptr(got[3]), B, C1, C2,
+                                        P, C1 * P, C2 * P, C1 * P, C2 * P, L.dptr(ct), C1 * P, L.dptr(ws), L.stream_ptr())
+    assert rc == 0, L.last_error()
+    torch.cuda.synchronize()
+    assert bool((ws[nbytes:] == 0xA5).all())
+    assert not bool((ws[:nbytes - 256] == 0xA5).all())            # (the call did use the workspace handed in)
+    for name, g, r in zip(("gx1", "gx2", "gw", "gb"), got, want):
+        assert torch.equal(g, r), name
+
+
 # ================================================================================================ element-wise
-# misc.hip / train.hip: float4 path iff n % 4 == 0 and every pointer is 16-byte aligned; stream_blocks caps the grid at
+# elementwise.hip / train.hip: float4 path iff n % 4 == 0 and every pointer is 16-byte aligned; stream_blocks caps the grid at
 # 4096 workgroups of 256 (one sweep = 4 * 4096 * 256 elements of the float4 path), blocks_for at 2048
 SWEEP = 4 * 4096 * 256
 EW_N = [1, 3, 4, 1023,
@@ -565,7 +605,7 @@ def test_gated_blend(ops, record_property, B, C, P):
 
 
 # ================================================================================================ bias grads
-# misc.hip: bias_grads_vec4_kernel iff P % 4 == 0, dz_bs % 4 == 0 and 16-byte aligned dz / gmap, else bias_grads_kernel;
+# elementwise.hip: bias_grads_vec4_kernel iff P % 4 == 0, dz_bs % 4 == 0 and 16-byte aligned dz / gmap, else bias_grads_kernel;
 # pchunks = min(2, ceil(P4 / 256), 2048 / C) workgroups per channel, their two atomic adds into gbias commute
 BG_CASES = [
     # (B, C, P, channel slice of a wider tensor, elements past a 16-byte boundary)

@@ -4,6 +4,7 @@
 #   tools/ab_step.sh "<extra hipcc flags for the GEMM units (gemm*.hip) of build B>" [rounds]
 # Run the build part locally (no GPU needed), the measuring part through gpurun.
 FLAGS=$1; ROUNDS=${2:-3}
+set -o pipefail
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/build/ab; mkdir -p $OUT
 if ! python3 -c "import torch,sys; sys.exit(0 if torch.cuda.is_available() else 1)" 2>/dev/null; then
@@ -19,7 +20,8 @@ fi
 for i in $(seq $ROUNDS); do
   for v in A B; do
     LIB=""; [ $v = B ] && LIB=$OUT/libparadis_hip_b.so
-    PARADIS_HIP_LIB=$LIB python3 $R/bench.py --no-cpu-baseline --no-exact-leg --no-kernel-events --steps 10 --warmup 3 2>/dev/null | tail -1 | \
-      python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', round(d['value'],1), 'samples/s', round(d['ms_per_step'],1), 'ms')"
+    PARADIS_HIP_LIB=$LIB timeout -k 10 600 python3 $R/bench.py --no-cpu-baseline --no-exact-leg --no-kernel-events --steps 10 --warmup 3 2>/dev/null | tail -1 | \
+      python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', round(d['value'],1), 'samples/s', round(d['ms_per_step'],1), 'ms')" \
+      || exit 1      # a run that failed or hung ends the comparison: nothing more is started on that device
   done
 done

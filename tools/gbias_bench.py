@@ -1,6 +1,6 @@
 """Diagnostic: the GlobalBias adjoint chain in isolation - projection adjoint (gPw, gm8 from the bias-map gradient) and
 the rank-R tail (gA, gU, gV from gm8) - at the three reference grids, Co = 1024, Cin = 8, R = 128.  PARADIS_HIP_LIB selects
-the build (tools/build_variant.sh ... misc.hip "-DGBIAS_GPW_ROWS=0" = one workgroup per (o, c) on every grid)."""
+the build (tools/build_variant.sh ... gbias.hip "-DGBIAS_GPW_ROWS=0" = one workgroup per (o, c) on every grid)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paradis_model_amd import ops

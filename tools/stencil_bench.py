@@ -1,9 +1,3 @@
-import os
-# needs the development build of the library (make -C paradis_model_amd/csrc dev): the shipped one exports
-# no paradis_debug_set_* tunables
-os.environ.setdefault("PARADIS_HIP_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
-                                                      "paradis_model_amd", "libparadis_hip_dev.so"))
-
 #!/usr/bin/env python3
 """Diagnostic: depthwise geo-conv and ChannelNorm kernels in isolation (cfg2 shapes), HIP-event times
 and effective bandwidth against the algorithmic bytes.  Usage on the GPU box: python tools/stencil_bench.py"""
@@ -54,20 +48,16 @@ def main():
         def fwd():
             nonlocal yy
             yy = ops.channel_norm(xx, wn, bn, 1e-5, xe)
-        for px in (64, 32):
-            lib.paradis_debug_set_norm_fwd_px(px)
-            t = timeit(fwd)
-            print(f"channel_norm fwd C={Cn}+{extra} px={px} {t:7.1f} us  {2 * nbn / t / 1e6:6.2f} TB/s")
+        t = timeit(fwd)
+        print(f"channel_norm fwd C={Cn}+{extra} {t:7.1f} us  {2 * nbn / t / 1e6:6.2f} TB/s")
 
         def bwd():
             xx.grad = None; wn.grad = None; bn.grad = None
             if xe is not None:
                 xe.grad = None
             yy.backward(g, retain_graph=True)
-        for rr in (0, 1):
-            lib.paradis_debug_set_norm_bwd_reread(rr)
-            t = timeit(bwd)
-            print(f"channel_norm bwd C={Cn}+{extra} reread={rr} {t:7.1f} us  {3 * nbn / t / 1e6:6.2f} TB/s (incl. autograd glue)")
+        t = timeit(bwd)
+        print(f"channel_norm bwd C={Cn}+{extra} {t:7.1f} us  {3 * nbn / t / 1e6:6.2f} TB/s (incl. autograd glue)")
 
 
 if __name__ == "__main__":
