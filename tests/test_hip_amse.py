@@ -208,13 +208,20 @@ def test_full_resolution_call_is_finite_and_recovers_a_synthesised_mode():
     H, W, C = 721, 1440, 97
     modes = {(40, 12): 1.5 - 0.5j}
     f = O.synth(H, W, modes).float()
-    p = f.view(1, 1, H, W).expand(1, C, H, W).contiguous().cuda().requires_grad_(True)
+    # channel c at the scale s_c = 1 + c / C, pred and target alike: the loss is homogeneous of degree 2 apart from the
+    # eps floor, so the value is mean_c(s_c^2) times that of one channel and grad[c] = s_c grad[0]; a plane written to
+    # the wrong channel shows
+    s = 1.0 + torch.arange(C, dtype=torch.float32) / C
+    p = (f.view(1, 1, H, W) * s.view(1, C, 1, 1)).contiguous().cuda().requires_grad_(True)
     t = (2.0 * p.detach()).contiguous()
     v = ops.amse_loss(p, t)
     v.backward()
     torch.cuda.synchronize()
     # pred's PSD at k = 40 is 2 |c|^2, the target's 4x that, coherence 1: amse_40 = 2|c|^2 (the rest sit at the eps floor)
     a = 2 * abs(1.5 - 0.5j) ** 2
-    want = (a + (H - 2) * 0.0) / (H - 1)
+    want = float((s.double() ** 2).mean()) * (a + (H - 2) * 0.0) / (H - 1)
     assert np.isfinite(float(v)) and abs(float(v) - want) <= 1e-3 * want, (float(v), want)
     assert bool(torch.isfinite(p.grad).all())
+    g = p.grad[0].cpu()
+    for c in range(C):
+        assert max_rel(g[c], float(s[c]) * g[0]) <= 1e-3, c
