@@ -489,6 +489,27 @@ int paradis_param_stats(const int64_t* ptrs, const int64_t* numel, const int* ch
                         const int* group_first_chunk, int n_tensors, int n_chunks, int n_groups, void* workspace,
                         float* out, void* stream);
 
+/* ---- global-norm gradient clipping over many tensors (ABI 10, additive): torch.nn.utils.clip_grad_norm_(params,
+ * max_norm, norm_type=2.0, error_if_nonfinite=False) - the reference's training.gradient_clip_val, train.py:52-53 - with
+ * fewer roundings.  At most three launches on `stream` (chunk partials, one finishing workgroup, scale), no host
+ * synchronisation, no memset or copy nodes, no atomics (bit-identical run to run).  Tables as paradis_adamw_multi_d:
+ * workgroup c works on at most paradis_clip_grad_chunk() elements of tensor chunk_tensor[c] from element chunk_off[c];
+ * grads [n_tensors] holds the addresses of the fp32 gradients, 0 = absent (neither read nor written); a table entry out
+ * of range reads nothing.  All tables DEVICE.
+ *   S = sum of g^2 over all present tensors, accumulated in double (an fp32 x fp32 product is exact in fp64);
+ *   out[0] = (float)sqrt(S);  c = max_norm / (sqrt(S) + 1e-6) in double;  out[1] = (float)(c < 1 ? c : (c is NaN ? c : 1));
+ *   every present gradient becomes g * out[1] in place, one fp32 multiply (skipped where out[1] is exactly 1.0f).
+ * A NaN gradient element gives out = {NaN, NaN} and all-NaN gradients, as torch does.
+ * max_norm must be finite and > 0 (rc 1 before any HIP call otherwise).  out: DEVICE fp32 [2].
+ * workspace: paradis_clip_grad_ws_bytes(n_chunks) bytes (one double per chunk), 8-byte aligned.
+ * n_chunks == 0 still writes out = {0, 1}.
+ * 16-byte loads and stores where a chunk start is 16-byte aligned, scalar otherwise: the same bits either way.
+ * Algorithmic HBM bytes: 4 per element (norm pass) + 8 per element (scale pass, when it clips). */
+int paradis_clip_grad_chunk(void);
+size_t paradis_clip_grad_ws_bytes(int n_chunks);
+int paradis_clip_grad_norm(const int64_t* grads, const int64_t* numel, const int* chunk_tensor, const int64_t* chunk_off,
+                           int n_tensors, int n_chunks, double max_norm, void* workspace, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

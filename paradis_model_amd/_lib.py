@@ -116,6 +116,9 @@ SIGNATURES = {
     "paradis_param_stats_chunk": (I, []),
     "paradis_param_stats_ws_bytes": (S, [I]),
     "paradis_param_stats": (I, [P, P, P, P, P, I, I, I, P, P, P]),
+    "paradis_clip_grad_chunk": (I, []),
+    "paradis_clip_grad_ws_bytes": (S, [I]),
+    "paradis_clip_grad_norm": (I, [P, P, P, P, I, I, D, P, P, P]),
 }
 
 _missing = []

@@ -37,10 +37,25 @@ struct Tab {
   __device__ __forceinline__ float* v(int t) const { return reinterpret_cast<float*>(p[3 * stride + t]); }
 };
 
-// m = mu m + g ; u = nesterov ? g + mu m : m ; sumsq[t] += sum u^2   (sumsq pre-zeroed)
+// The norm sums of the step are reduced in a FIXED order (no float atomics): every producing workgroup stores its partial
+// sum, every consuming workgroup adds the partials of its matrix the same way - thread i takes p[i], p[i + 256], ..,
+// then the shuffle butterfly and the four waves through LDS.  Two identical steps give identical bits.  The same value in
+// every thread of the 256-thread workgroup.
+__device__ __forceinline__ float block_sum_fixed(const float* __restrict__ p, int count, float* red /* LDS [4] */) {
+  float a = 0.f;
+  for (int i = threadIdx.x; i < count; i += 256) a += p[i];
+  a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  const float s = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return s;
+}
+
+// m = mu m + g ; u = nesterov ? g + mu m : m ; part[t][blockIdx.x] = this workgroup's sum u^2
 __global__ void __launch_bounds__(256)
 muon_momentum_kernel(Tab tab, float* __restrict__ U, int64_t n, float mu, int nesterov,
-                     float* __restrict__ sumsq) {
+                     float* __restrict__ part) {
   __shared__ float red[4];
   const int t = blockIdx.y;
   float* m = tab.m(t);
@@ -58,15 +73,16 @@ muon_momentum_kernel(Tab tab, float* __restrict__ U, int64_t n, float mu, int ne
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(&sumsq[t], red[0] + red[1] + red[2] + red[3]);
+  if (threadIdx.x == 0) part[(int64_t)t * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// y_t = x_t / (sqrt(sumsq[t]) + eps)
+// y_t = x_t / (sqrt(sum of part[t][0 .. gridDim.x)) + eps); same grid as muon_momentum_kernel
 __global__ void __launch_bounds__(256)
 muon_normalize_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n,
-                      const float* __restrict__ sumsq, float eps) {
+                      const float* __restrict__ part, float eps) {
+  __shared__ float red[4];
   const int t = blockIdx.y;
-  const float inv = 1.0f / (sqrtf(sumsq[t]) + eps);
+  const float inv = 1.0f / (sqrtf(block_sum_fixed(part + (int64_t)t * gridDim.x, (int)gridDim.x, red)) + eps);
   x += (int64_t)t * n; y += (int64_t)t * n;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = x[i] * inv;
 }
@@ -99,10 +115,10 @@ muon_poly_kernel(const float* __restrict__ A, const float* __restrict__ A2, floa
 
 // NorMuon, one block per neuron (row of the un-transposed matrix) of matrix t = blockIdx.y:
 // v[r] = beta2 v[r] + (1-beta2) mean_c x[r,c]^2 ; x[r,:] /= sqrt(v[r]) + 1e-8 ;
-// sums[2t] += sum x_old^2 ; sums[2t+1] += sum x_new^2
+// part_old[t][r] = sum x_old[r,:]^2 ; part_new[t][r] = sum x_new[r,:]^2
 __global__ void __launch_bounds__(256)
 normuon_rows_kernel(float* __restrict__ X, Tab tab, int rows, int cols, int64_t rs, int64_t cs, float beta2,
-                    float* __restrict__ sums) {
+                    float* __restrict__ part_old, float* __restrict__ part_new) {
   __shared__ float red[4];
   __shared__ float stat;
   const int r = blockIdx.x, t = blockIdx.y;
@@ -122,16 +138,16 @@ normuon_rows_kernel(float* __restrict__ X, Tab tab, int rows, int cols, int64_t 
     v[r] = vn;
     const float inv = 1.0f / (sqrtf(vn) + 1e-8f);
     stat = inv;
-    atomicAdd(&sums[2 * t], ss);
-    atomicAdd(&sums[2 * t + 1], ss * inv * inv);
+    part_old[(int64_t)t * rows + r] = ss;
+    part_new[(int64_t)t * rows + r] = ss * inv * inv;
   }
   __syncthreads();
   const float inv = stat;
   for (int c = threadIdx.x; c < cols; c += 256) x[(int64_t)r * rs + (int64_t)c * cs] *= inv;
 }
 
-// w_t = w_t (1 - lr wd) - alpha ratio_t u_t,  ratio = sqrt(sums[2t]) / max(sqrt(sums[2t+1]), 1e-8) when
-// sums given; u is read with strides (it may be held transposed).
+// w_t = w_t (1 - lr wd) - alpha ratio_t u_t,  ratio = sqrt(sum part_old[t]) / max(sqrt(sum part_new[t]), 1e-8) when
+// the partials of normuon_rows_kernel are given; u is read with strides (it may be held transposed).
 // dev (optional): {int32 step, bits of the fp32 lr} of the group on the device (the layout of adamw_multi_kernel): the
 // two coefficients that depend on the learning rate are then formed here, so that a HIP graph captured around the step
 // holds no learning rate in its kernel arguments.  decay = 1 - lr wd in fp32 with the product rounded on its own (what
@@ -139,8 +155,9 @@ normuon_rows_kernel(float* __restrict__ X, Tab tab, int rows, int cols, int64_t 
 // Python's double product): the two paths agree to 1 ulp of the coefficients.
 __global__ void __launch_bounds__(256)
 muon_apply_kernel(Tab tab, const float* __restrict__ U, int rows, int cols, int64_t urs, int64_t ucs,
-                  float decay, float alpha, const float* __restrict__ sums, const int* __restrict__ dev, float wd,
-                  double lr_scale) {
+                  float decay, float alpha, const float* __restrict__ part_old, const float* __restrict__ part_new,
+                  const int* __restrict__ dev, float wd, double lr_scale) {
+  __shared__ float red[4];
   const int t = blockIdx.y;
   if (dev) {     // (uniform over the grid)
 #pragma clang fp contract(off)     // lr * wd rounded on its own, as the host forms it: no fma(-lr, wd, 1)
@@ -150,7 +167,11 @@ muon_apply_kernel(Tab tab, const float* __restrict__ U, int rows, int cols, int6
     alpha = (float)((double)lr * lr_scale);
   }
   float ratio = 1.0f;
-  if (sums) ratio = sqrtf(sums[2 * t]) / fmaxf(sqrtf(sums[2 * t + 1]), 1e-8f);
+  if (part_old) {     // (uniform over the grid)
+    const float s_old = block_sum_fixed(part_old + (int64_t)t * rows, rows, red);
+    const float s_new = block_sum_fixed(part_new + (int64_t)t * rows, rows, red);
+    ratio = sqrtf(s_old) / fmaxf(sqrtf(s_new), 1e-8f);
+  }
   const float k = alpha * ratio;
   const int64_t n = (int64_t)rows * cols;
   float* w = tab.w(t);
@@ -170,7 +191,7 @@ inline size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }
 extern "C" size_t paradis_muon_ws_bytes(int T, int rows, int cols) {
   if (T <= 0 || rows <= 0 || cols <= 0) return 256;
   const size_t n = (size_t)rows * cols, m = (size_t)std::min(rows, cols);
-  // U, X, XT, Xnew (T x n each), A, A2, B' (T x m x m each), scalars; then the bf16-split images of the
+  // U, X, XT, Xnew (T x n each), A, A2, B' (T x m x m each), 3 T + 64 unused floats (formerly the norm scalars); then the bf16-split images of the
   // left operands of the Newton-Schulz products (T x [m, max(rows, cols)], 256-B aligned)
   const size_t floats = (up64(n * T)) * 4 + up64(m * m * T) * 3 + up64(3 * (size_t)T) + 64;
   return floats * sizeof(float) + (size_t)T * paradis_pw_gemm_split_bytes((int)m, std::max(rows, cols), PARADIS_GEMM_BF16X3) + 256;
@@ -205,26 +226,25 @@ extern "C" int paradis_muon_step_d(const int64_t* ptrs, int table_stride, int T,
   float* A = ws;                 ws += up64((size_t)mm * T);
   float* A2 = ws;                ws += up64((size_t)mm * T);
   float* Bp = ws;                ws += up64((size_t)mm * T);
-  float* sc = ws;                // [T] sum u^2, then [2T] NorMuon sums
-  ws += up64(3 * (size_t)T) + 64;
+  ws += up64(3 * (size_t)T) + 64;      // (unused: the norm sums were scalars here before they became fixed-order partials;
+                                       //  skipped so that paradis_muon_ws_bytes and the alignment of `img` stay as they were)
   // split != 0: the three products of every iteration run on the bf16-split GEMM (gemm.hip); the images
   // of their left operands ([M,K] or [M,M], K >= M) live behind the float workspace
   void* img = split ? (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) : nullptr;
-  if (pd_zero_async(sc, 3 * (size_t)T * sizeof(float), st) != hipSuccess) {
-    paradis_set_error("muon_step: memset failed");
-    return 2;
-  }
   const dim3 gn(blocks(n), T);
-  hipLaunchKernelGGL(muon_momentum_kernel, gn, dim3(256), 0, st, tab, U, n, mu, nesterov, sc);
+  // the partial sums live in regions of the workspace that are idle when they are written and read: blocks(n) * T <= n * T
+  // floats of Xn (first written by the third product of the first iteration) for sum u^2 ...
+  float* part_u = Xn;
+  hipLaunchKernelGGL(muon_momentum_kernel, gn, dim3(256), 0, st, tab, U, n, mu, nesterov, part_u);
   // X = U / (||U|| + eps), in the wide orientation [M, K]
   auto transpose = [&](const float* in, float* out, int r, int c) {
     hipLaunchKernelGGL(muon_transpose_kernel, dim3((c + 31) / 32, (r + 31) / 32, T), dim3(256), 0, st, in, out, r, c);
   };
   if (tr) {
-    hipLaunchKernelGGL(muon_normalize_kernel, gn, dim3(256), 0, st, (const float*)U, XT, n, (const float*)sc, eps);
+    hipLaunchKernelGGL(muon_normalize_kernel, gn, dim3(256), 0, st, (const float*)U, XT, n, (const float*)part_u, eps);
     transpose(XT, X, rows, cols);                                                                       // X [M, K]
   } else {
-    hipLaunchKernelGGL(muon_normalize_kernel, gn, dim3(256), 0, st, (const float*)U, X, n, (const float*)sc, eps);
+    hipLaunchKernelGGL(muon_normalize_kernel, gn, dim3(256), 0, st, (const float*)U, X, n, (const float*)part_u, eps);
   }
   float* cur = X;
   float* nxt = Xn;
@@ -243,11 +263,15 @@ extern "C" int paradis_muon_step_d(const int64_t* ptrs, int table_stride, int T,
   // cur = orthogonalised updates in the wide orientation; element (r, c) of the [rows, cols] matrix is
   // cur[c*K + r] when transposed, cur[r*K + c] otherwise
   const int64_t urs = tr ? 1 : K, ucs = tr ? K : 1;
+  // ... and rows * T <= n * T floats each of the iteration's other buffer and of XT for NorMuon's two row sums (cur is the
+  // result; nxt and XT are not read again)
+  float* part_old = normuon ? nxt : nullptr;
+  float* part_new = normuon ? XT : nullptr;
   if (normuon)
     hipLaunchKernelGGL(normuon_rows_kernel, dim3(rows, T), dim3(256), 0, st, cur, tab, rows, cols, urs, ucs, beta2,
-                       sc + T);
+                       part_old, part_new);
   hipLaunchKernelGGL(muon_apply_kernel, gn, dim3(256), 0, st, tab, (const float*)cur, rows, cols, urs, ucs,
-                     1.0f - lr * weight_decay, lr_adj, normuon ? (const float*)(sc + T) : (const float*)nullptr, dev_state,
+                     1.0f - lr * weight_decay, lr_adj, (const float*)part_old, (const float*)part_new, dev_state,
                      weight_decay, lr_scale);
   PD_CHECK_LAUNCH("muon_step");
   return 0;

@@ -119,6 +119,15 @@ def rollout_loss(model, loss_fn, batch, *, num_common: int, n_inputs: int, accum
     return total, outs
 
 
+def _wgrad_side_stream() -> bool:
+    """is the opt-in side stream of the weight-gradient GEMMs on (``ops.WgradSide``, PARADIS_WGRAD_STREAM=1)"""
+    import sys
+    ops = sys.modules.get(__package__ + ".ops")
+    if ops is not None:
+        return bool(ops.WgradSide.enabled)
+    return os.environ.get("PARADIS_WGRAD_STREAM", "0") == "1"
+
+
 class TrainStep:
     """forward(S rollout steps) + ParadisLoss + backward + AdamW, the unit the benchmark times
     (SURVEY.md section 8d).  AdamW hyper-parameters follow reference trainer.py:327-335.
@@ -131,12 +140,50 @@ class TrainStep:
     ``LambdaLR`` with interval ``"step"`` (trainer.py:416-456), tabulated once (``schedule.DeviceSchedule``).  A capturable
     optimiser reads the table on the device, one launch inside ``opt.step()`` (so inside a captured graph); any other
     optimiser gets ``group["lr"]`` set from the same table before every ``opt.step()``.  ``None``: the learning rate is
-    whatever ``group["lr"]`` holds."""
+    whatever ``group["lr"]`` holds.  Schedules advance per optimiser step, not per call.
+
+    ``accumulate_grad_batches`` (``None``: ``cfg.training.accumulate_grad_batches``, default 1): a call is ONE micro-batch
+    with the reference's gating (trainer.py:503-506, 560, 578-587) on the number of micro-batches since the last optimiser
+    step: the gradients are zeroed on the first batch of a window, the loss is divided by ``S * N``, and the optimiser (and
+    the schedule) step on the N-th.  A call returns the reference's ``train_loss`` of its batch (trainer.py:589: the rollout
+    mean WITHOUT the 1/N).  ``pending``: micro-batches accumulated since the last optimiser step; ``flush()``: the
+    reference's ``is_last_batch`` - steps with what is there (the gradients still carry 1/N); ``window(batches)``: N calls,
+    the stacked ``[N]`` losses.
+
+    ``gradient_clip_val`` (``None``: ``cfg.training.gradient_clip_val``; ``None`` or 0: off, Lightning's rule): global-norm
+    clipping (``clip.clip_grad_norm_``, reference train.py:52-53) of every parameter of ``opt.param_groups`` that has a
+    gradient, between the last backward (and the statistics, which see the unclipped gradients: Lightning's hook order)
+    and the optimiser step.  ``last_grad_norm``: fp32 ``[2]`` on the device, ``{norm before clipping, coefficient}`` of the
+    most recent optimiser step; ``None`` with clipping off.
+
+    With N = 1 and clipping off the step launches exactly what it launched before these two controls existed."""
 
     def __init__(self, model, loss_fn, cfg, *, num_common: int = 83, n_inputs: int = 2, fused=None,
-                 capturable: bool = False, amp: bool = False, stats=None, schedule=None):
+                 capturable: bool = False, amp: bool = False, stats=None, schedule=None,
+                 accumulate_grad_batches=None, gradient_clip_val=None):
         self.model, self.loss_fn = model, loss_fn
         self.stats = stats
+        if accumulate_grad_batches is None:
+            accumulate_grad_batches = cfg.training.get("accumulate_grad_batches", 1)
+        if gradient_clip_val is None:
+            gradient_clip_val = cfg.training.get("gradient_clip_val", None)
+        if isinstance(accumulate_grad_batches, bool) or not isinstance(accumulate_grad_batches, int) \
+                or accumulate_grad_batches < 1:
+            raise ValueError(f"accumulate_grad_batches must be an int >= 1, got {accumulate_grad_batches!r}")
+        self.accumulate = accumulate_grad_batches
+        if gradient_clip_val is not None:
+            gradient_clip_val = float(gradient_clip_val)
+            if not math.isfinite(gradient_clip_val) or gradient_clip_val < 0:
+                raise ValueError(f"gradient_clip_val must be finite and >= 0, got {gradient_clip_val!r}")
+        self.clip_val = gradient_clip_val or None          # None or 0: off
+        if self.accumulate > 1 and stats is not None:
+            raise ValueError("stats= together with accumulate_grad_batches > 1: per-window statistics are not supported")
+        if self.accumulate > 1 and _wgrad_side_stream():
+            raise ValueError("accumulate_grad_batches > 1 with PARADIS_WGRAD_STREAM=1: the side stream hands its "
+                             "gradients over safely only while .grad is None")
+        self.pending = 0              # micro-batches accumulated since the last optimiser step
+        self.last_grad_norm = None
+        self._clip_plan = None
         # amp: forward and loss under torch.autocast(bfloat16) - the reference's shipped ``use_amp: true`` /
         # ``precision="bf16-mixed"`` (config/paradis_settings.yaml:75, train.py:56); parameters, gradients and the
         # optimiser stay fp32, as with Lightning's mixed-precision plugin
@@ -178,24 +225,69 @@ class TrainStep:
                 self.schedule = table
 
     def __call__(self, batch):
-        self.opt.zero_grad(set_to_none=True)
+        N = self.accumulate
+        if self.pending == 0:
+            self.opt.zero_grad(set_to_none=True)
         stats = self.stats
         if stats is None:
-            loss, _ = rollout_loss(self.model, self.loss_fn, batch, num_common=self.num_common,
+            loss, _ = rollout_loss(self.model, self.loss_fn, batch, num_common=self.num_common, accum=N,
                                    n_inputs=self.n_inputs, detach_every=self.detach_every, amp=self.amp)
         else:
             stats.begin_step()
             loss, _ = rollout_loss(self.model, self.loss_fn, batch, num_common=self.num_common,
                                    n_inputs=self.n_inputs, detach_every=self.detach_every, amp=self.amp,
                                    on_step=stats.on_rollout_step)
-            stats.before_optimizer_step(self.opt)
-            stats.record_loss(loss)
+        self.pending += 1
+        if self.pending == N:
+            if stats is not None:
+                stats.before_optimizer_step(self.opt)      # in front of the clip: the statistics see unclipped gradients
+                stats.record_loss(loss)
+            self._optimizer_step()
+        return loss if N == 1 else loss * N
+
+    def _optimizer_step(self):
+        if self.clip_val is not None:
+            self.last_grad_norm = self._clip()
         if self.schedule is not None:
             for gi, group in enumerate(self.opt.param_groups):
                 group["lr"] = self.schedule.host_lr(gi, self.opt_steps)
         self.opt.step()
         self.opt_steps += 1
-        return loss
+        self.pending = 0
+
+    def _clip(self):
+        from . import clip
+        params = [p for group in self.opt.param_groups for p in group["params"]]
+        if params and params[0].is_cuda:
+            # the step owns its plan instead of taking ``clip.plan_for``'s: a captured graph reads this plan's tables and
+            # ``out`` on every replay, so the small global cache must never be able to evict (free) it
+            key = tuple((id(p), p.numel()) for p in params) + (str(params[0].device),)
+            if self._clip_plan is None or self._clip_plan[0] != key:
+                self._clip_plan = (key, clip.ClipPlan([p.numel() for p in params], params[0].device))
+            return clip.clip_grad_norm_(params, self.clip_val, plan=self._clip_plan[1])
+        return clip.clip_grad_norm_(params, self.clip_val)
+
+    @property
+    def clip_plan(self):
+        """the ``clip.ClipPlan`` of this step's clipping on the HIP device (``None`` before the first clipped step)"""
+        return None if self._clip_plan is None else self._clip_plan[1]
+
+    def flush(self) -> bool:
+        """the reference's ``is_last_batch`` (trainer.py:578-587): an optimiser step on the micro-batches accumulated so
+        far, if any (their gradients still carry the 1/N of a full window); returns whether it stepped"""
+        if self.pending == 0:
+            return False
+        self._optimizer_step()
+        return True
+
+    def window(self, batches):
+        """one whole accumulation window: ``len(batches) == accumulate_grad_batches`` calls, the stacked ``[N]`` losses"""
+        batches = list(batches)
+        if self.pending != 0:
+            raise ValueError(f"window(): {self.pending} micro-batches are pending; flush() first")
+        if len(batches) != self.accumulate:
+            raise ValueError(f"window(): {len(batches)} batches for accumulate_grad_batches = {self.accumulate}")
+        return torch.stack([self(b) for b in batches])
 
 
 class GraphedTrainStep:
@@ -220,22 +312,43 @@ class GraphedTrainStep:
     notes for DDP): the wrapper constructed on a side stream, at least 11 eager DDP iterations before the capture (the
     Reducer rebuilds its buckets after the first one and settles its bookkeeping over the next ones), and no
     asynchronous NCCL error handling thread touching the captured work (TORCH_NCCL_ASYNC_ERROR_HANDLING=0, set by
-    ``init_distributed(capturable=True)``)."""
+    ``init_distributed(capturable=True)``).
+
+    Gradient clipping (``TrainStep(gradient_clip_val=...)``) and truncated BPTT (``detach_gradient_every``) are simply
+    captured with the step.  With ``accumulate_grad_batches`` = N > 1 the unit of capture is the WINDOW: ``example_batch``
+    is a sequence of N batches, ``__call__(batches)`` copies N batches into the static buffers, makes ONE replay and returns
+    the static ``[N]`` losses; ``eager_step(batches)`` runs ``TrainStep.window``.  A DDP-wrapped model with N > 1 is not
+    supported under capture yet (eager DDP with N > 1 works as in the reference: one all-reduce round per backward)."""
 
     DDP_WARMUP = 11
 
     def __init__(self, step: TrainStep, example_batch, warmup: int = 2):
         if not getattr(step.opt, "capturable", False):
             raise ValueError("GraphedTrainStep needs TrainStep(..., capturable=True)")
+        self.windowed = step.accumulate > 1
         if isinstance(step.model, torch.nn.parallel.DistributedDataParallel):
+            if self.windowed:
+                raise ValueError("GraphedTrainStep: a DistributedDataParallel model with accumulate_grad_batches > 1 is "
+                                 "not supported under capture yet")
             warmup = max(warmup, self.DDP_WARMUP)
+        if step.pending != 0:
+            raise ValueError(f"GraphedTrainStep: {step.pending} micro-batches are pending; flush() first")
         self.step = step
-        self.static_batch = tuple(t.clone() for t in example_batch)
+        if self.windowed:
+            example_batch = list(example_batch)
+            if len(example_batch) != step.accumulate or not all(isinstance(b, (tuple, list)) for b in example_batch):
+                raise ValueError(f"GraphedTrainStep: example_batch must be a sequence of {step.accumulate} batches "
+                                 "(accumulate_grad_batches)")
+            self.static_batch = [tuple(t.clone() for t in b) for b in example_batch]
+            run = step.window
+        else:
+            self.static_batch = tuple(t.clone() for t in example_batch)
+            run = step
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                step(self.static_batch)
+                run(self.static_batch)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.warmup_steps = max(1, warmup)
@@ -254,26 +367,39 @@ class GraphedTrainStep:
             import time as _time
             _time.sleep(0.25)
         with torch.cuda.graph(self.graph, capture_error_mode=mode):
-            self.static_loss = step(self.static_batch)
+            self.static_loss = run(self.static_batch)
         # the graph's optimiser nodes copy the pinned pointer tables of the capture on every replay: keep a snapshot
         # (and the captured gradient tensors, which live in the graph's private pool) for eager_step()
         self._tables = step.opt.snapshot_pointer_tables()
         stats = getattr(step, "stats", None)      # the statistics launches were captured with the step: same for their table
         self._stats_table = stats.snapshot_pointer_tables() if stats is not None else None
+        plan = step.clip_plan                     # ... and for the gradient address row of the clip
+        self._clip_table = plan.snapshot_pointer_tables() if plan is not None else None
         self._captured_grads = [p.grad for g in step.opt.param_groups for p in g["params"]]
         # the capture ran the Python side of one step (host step counts advanced) without executing it on the
         # device: bring the device-side count of the captured tick back in line on first replay
         self._first = True
         self._replayed = torch.cuda.Event()
 
+    def _pairs(self, batch):
+        """(static batch, given batch) pairs: one, or the N of a window"""
+        if not self.windowed:
+            return [(self.static_batch, batch)]
+        batch = list(batch)
+        if len(batch) != len(self.static_batch):
+            raise ValueError(f"GraphedTrainStep: {len(batch)} batches for a window of {len(self.static_batch)}")
+        return list(zip(self.static_batch, batch))
+
     def __call__(self, batch):
-        for dst, src in zip(self.static_batch, batch):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src, non_blocking=True)
+        for static, given in self._pairs(batch):
+            for dst, src in zip(static, given):
+                if dst.data_ptr() != src.data_ptr():
+                    dst.copy_(src, non_blocking=True)
         if self._first:
             self._first = False      # host counters already include this step (incremented during capture)
         else:
             self.step.opt.note_replayed()
+            self.step.opt_steps += 1
         self.graph.replay()
         self._replayed.record()      # eager_step() waits for it before it touches the optimiser's pointer tables
         # the replay rewrites the parameters through raw pointers: no autograd version bump, no optimiser post-hook.
@@ -294,12 +420,16 @@ class GraphedTrainStep:
         there yet (any GPU-bound configuration: ~150 ms of device time against ~30 ms of host enqueue), and that
         replay would apply AdamW with the eager step's gradient addresses.  So the host first waits for the last
         replay to finish (ADVICE r4; ``tests/test_hip_graph.py::test_eager_step_right_behind_a_gpu_bound_replay``).
-        The pinned address table of a ``TrainStep(stats=...)``'s statistics is snapshotted and restored the same way."""
+        The pinned address table of a ``TrainStep(stats=...)``'s statistics and the address row of its clip are
+        snapshotted and restored the same way.  With ``accumulate_grad_batches`` > 1, ``batch`` is a window of N batches
+        (``TrainStep.window``) and the ``[N]`` losses are returned."""
         self._replayed.synchronize()
-        loss = self.step(batch)
+        loss = self.step.window(batch) if self.windowed else self.step(batch)
         self.step.opt.restore_pointer_tables(self._tables)
         if self._stats_table is not None:
             self.step.stats.restore_pointer_tables(self._stats_table)
+        if self._clip_table is not None:
+            self.step.clip_plan.restore_pointer_tables(self._clip_table)
         return loss
 
 
