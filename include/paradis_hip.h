@@ -510,6 +510,32 @@ size_t paradis_clip_grad_ws_bytes(int n_chunks);
 int paradis_clip_grad_norm(const int64_t* grads, const int64_t* numel, const int* chunk_tensor, const int64_t* chunk_off,
                            int n_tensors, int n_chunks, double max_norm, void* workspace, float* out, void* stream);
 
+/* ---- forecast verification (ABI 10, additive): latitude-weighted RMSE, bias, MAE, anomaly correlation and activity
+ * per (lead, channel), WeatherBench-2's conventions.  One launch pair on `stream`, no host synchronisation, no memset or
+ * copy nodes, no atomics (bit-identical run to run); neither input is written.
+ *   fc, truth [B, C, H, W] fp32 in physical units, dense [C, H, W] states, batch strides fc_bs / truth_bs in elements;
+ *   lat_w [H] fp32 >= 0 (DEVICE);  Z = W * sum_h lat_w[h], formed in double by the caller;
+ *   clim [K, C, H, W] fp32 dense and clim_index [B] int32 (DEVICE, 0 <= k < K: the slot of sample b; a slot out of
+ *   range is not read and turns the sums of its sample into NaN), or both NULL.
+ * Per sample b and channel c over the plane, w = lat_w[h], fa = f - clim[k[b]], ta = t - clim[k[b]]:
+ *   se = sum w (f-t)^2 / Z,  e = sum w (f-t) / Z,  ae = sum w |f-t| / Z,
+ *   ff = sum w fa^2,  tt = sum w ta^2,  ft = sum w fa ta,  acc_b = ft / sqrt(ff tt)
+ *   acc[c][0..7] += {1, se, e, ae, acc_b, 1, ff, tt}     (acc_b and its 1 are left out when ff tt == 0)
+ * acc: DEVICE double [C][8], the row of this lead, read and written by an ordinary read-modify-write (calls on one
+ * stream are ordered); without a climatology entries 4 .. 7 are not touched.  Non-finite inputs are not masked.
+ * Sums: fp32 per thread over at most paradis_verify_piece() / 256 cells, double from there on, in a fixed order.
+ * ws: paradis_verify_ws_bytes(B, C, H, W, with_clim) bytes, 8-byte aligned: double [6 with a climatology, else 3]
+ * [B*C][ceil(H*W / paradis_verify_piece())].  B == 0 does nothing.  rc 1 before any HIP call for: clim without
+ * clim_index or the reverse, C / H / W < 1, K < 1 with a climatology, Z <= 0 or non-finite, a NULL acc or ws, a grid
+ * above the launch limit.
+ * W % 4 == 0 with 16-byte aligned planes takes 16-byte loads, anything else scalar loads: the same bits either way.
+ * Algorithmic HBM bytes: 12*B*C*H*W with a climatology, 8*B*C*H*W without. */
+int paradis_verify_piece(void);
+size_t paradis_verify_ws_bytes(int B, int C, int H, int W, int with_clim);
+int paradis_verify_update(const float* fc, int64_t fc_bs, const float* truth, int64_t truth_bs, const float* clim,
+                          const int* clim_index, int K, const float* lat_w, double Z, double* acc, void* ws, int B,
+                          int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

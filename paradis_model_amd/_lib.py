@@ -119,6 +119,9 @@ SIGNATURES = {
     "paradis_clip_grad_chunk": (I, []),
     "paradis_clip_grad_ws_bytes": (S, [I]),
     "paradis_clip_grad_norm": (I, [P, P, P, P, I, I, D, P, P, P]),
+    "paradis_verify_piece": (I, []),
+    "paradis_verify_ws_bytes": (S, [I, I, I, I, I]),
+    "paradis_verify_update": (I, [P, L, P, L, P, P, I, P, D, P, P, I, I, I, I, P]),
 }
 
 _missing = []

@@ -277,7 +277,15 @@ class Forecaster:
     ``graph=True``: the forward step is captured into a HIP graph per (B, H, W) after an eager warm-up, outside
     ``ops.frozen_weights()`` - the weight-image kernels are nodes of the graph, so parameters written in place between
     runs (``load_state_dict``, an optimiser step) are honoured by the next replay.  Per step the host then issues one
-    forcing copy, one replay and (stored steps) one post-processing launch."""
+    forcing copy, one replay and (stored steps) one post-processing launch.
+
+    ``run(..., scorecard=<verify.Scorecard>, truth=<[B, n_stored, C, H, W] on the device>, truth_normalized=False,
+    clim_index=<int32 [B, n_stored] or None>)``: right after the post-processing of stored state ``k`` the finished state
+    is scored in place against ``truth[:, k]`` at lead ``k`` (``scorecard.update``, one launch pair on the main stream, in
+    front of the event the side-stream copy waits for).  ``truth_normalized=True``: the truth is in model space (a
+    validation batch's ``true_data``) and goes through the same ``postprocess`` into a scratch state first.  Without a
+    scorecard ``run`` issues exactly the launches it issued before; a scorecard without ``truth``, or a truth of another
+    ``n_stored``, is refused before the rollout starts."""
 
     def __init__(self, model, spec: PostSpec, lat_deg, lon_deg, *, num_common: int = 83, n_inputs: int = 2,
                  output_frequency: int = 1, write_every_n: Optional[int] = None, graph: bool = True,
@@ -291,6 +299,7 @@ class Forecaster:
         self.dewpoint = spec.dewpoint if dewpoint is None else bool(dewpoint)
         self._steps = {}       # (B, H, W) -> _GraphedStep
         self._bufs = {}        # chunk shape -> device chunks, pinned buffers, events
+        self._truth = {}       # (B, C, H, W, device) -> [B, 1, C, H, W]: a model-space truth state in physical units
 
     def _buffers(self, B, n, C, L, H, W, device):
         key = (B, n, C, L, H, W, str(device), self.dewpoint)
@@ -307,9 +316,38 @@ class Forecaster:
                                    [False, False])
         return self._bufs[key]
 
+    def _check_verification(self, scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W):
+        """the refusals of ``run(scorecard=...)``, before the rollout starts; returns the forecaster's ``[B, 1, C, H, W]``
+        scratch tensor for a model-space truth (``truth_normalized=True``), else None"""
+        if scorecard is None:
+            if truth is not None or clim_index is not None or truth_normalized:
+                raise ValueError("Forecaster.run: truth, truth_normalized and clim_index go with a scorecard")
+            return None
+        if truth.dim() != 5 or tuple(truth.shape) != (B, n_stored, C, H, W) or truth.dtype != torch.float32:
+            raise ValueError(f"Forecaster.run: truth must be float32 {(B, n_stored, C, H, W)} (n_stored = {n_stored} "
+                             f"stored states), got {truth.dtype} {tuple(truth.shape)}")
+        if scorecard.n_leads < n_stored:
+            raise ValueError(f"Forecaster.run: the scorecard has {scorecard.n_leads} leads, the rollout stores {n_stored}")
+        if list(scorecard.names) != list(self.spec.names):
+            raise ValueError("Forecaster.run: the scorecard's names are not the chunk's channel names (PostSpec.names)")
+        if clim_index is not None and (clim_index.dtype != torch.int32 or tuple(clim_index.shape) != (B, n_stored)):
+            raise ValueError(f"Forecaster.run: clim_index must be int32 {(B, n_stored)}, got {clim_index.dtype} "
+                             f"{tuple(clim_index.shape)}")
+        require_hip(truth)
+        if not truth_normalized:
+            return None
+        key = (B, C, H, W, str(truth.device))
+        if key not in self._truth:
+            with torch.inference_mode(False):
+                self._truth[key] = torch.empty(B, 1, C, H, W, device=truth.device)
+        return self._truth[key]
+
     @torch.no_grad()
     def run(self, input_data, forcings, constants, on_chunk: Optional[Callable],
-            forecast_steps: Optional[int] = None):
+            forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
+            truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None):
+        if scorecard is not None and truth is None:          # (a host-side refusal, in front of the device checks)
+            raise ValueError("Forecaster.run: a scorecard needs truth [B, n_stored, C, H, W] on the device")
         require_hip(input_data, forcings, constants)
         S = int(forcings.shape[1] if forecast_steps is None else forecast_steps)
         if forcings.shape[1] < S:
@@ -318,6 +356,7 @@ class Forecaster:
         n_stored = sum(p.stored for p in plan)
         B, _, _, H, W = input_data.shape
         C, L = self.spec.num_channels, self.spec.num_levels
+        truth_phys = self._check_verification(scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W)
         n_chunk = min(n_stored, S if self.write_every_n is None else int(self.write_every_n))
         dev, host, ddev, dhost, filled, copied, side, used = self._buffers(B, n_chunk, C, L, H, W, input_data.device)
         main = torch.cuda.current_stream()
@@ -353,6 +392,7 @@ class Forecaster:
 
         pending = None         # (buffer index, start_idx, n) enqueued for copy, not yet handed over
         i_chunk = 0
+        i_stored = 0
         for step, p in enumerate(plan):
             if step_fn is not None:
                 out = step_fn(forc[:, step])
@@ -367,6 +407,13 @@ class Forecaster:
                     if used[k]:
                         main.wait_event(copied[k])     # the side stream has finished reading this device chunk
                 postprocess(out, self.spec, self.lat_deg, self.lon_deg, d, p.slot, dd)
+                if scorecard is not None:      # on the main stream, in front of `filled`: the copy sees a finished chunk
+                    t = truth[:, i_stored]
+                    if truth_phys is not None:
+                        postprocess(t, self.spec, self.lat_deg, self.lon_deg, truth_phys, 0)
+                        t = truth_phys[:, 0]
+                    scorecard.update(i_stored, d[:, p.slot], t, None if clim_index is None else clim_index[:, i_stored])
+                i_stored += 1
             if p.flush is not None:
                 start, n = p.flush
                 filled[k].record(main)

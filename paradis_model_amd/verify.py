@@ -1,0 +1,216 @@
+"""Forecast verification: how RMSE, bias, MAE, anomaly correlation (ACC) and activity grow with lead time, for every
+variable of a forecast chunk, in physical units - the deterministic scores of WeatherBench-2, accumulated on the device.
+
+Conventions.  Forecast ``f`` and truth ``t`` are ``[B, C, H, W]`` fp32 in physical units, in the chunk layout of
+``forecast.postprocess`` (with ``winds=True``: ``u, v, w`` where ``wind_x, wind_y, wind_z`` were).  ``w[h] >= 0`` are
+latitude weights (``[H]``, not all zero), ``Z = W * sum_h w[h]`` (formed in double on the host).  An optional
+climatology ``clim [K, C, H, W]`` comes with an index ``k[b]`` (int32 on the device, ``0 <= k < K``) that names the
+climatology slot of sample ``b`` at this lead.  Per sample ``b`` and channel ``c``, sums over the plane, with
+``fa = f - clim[k[b]]`` and ``ta = t - clim[k[b]]``::
+
+    se = sum w (f-t)^2 / Z      e  = sum w (f-t) / Z      ae = sum w |f-t| / Z
+    ff = sum w fa^2             tt = sum w ta^2            ft = sum w fa ta
+    acc_b = ft / sqrt(ff * tt)       (the sample is left out of the ACC mean when ff * tt == 0)
+
+Accumulated per (lead, channel), eight doubles: ``{n, sum se, sum e, sum ae, sum acc_b, n_acc, sum ff, sum tt}``.
+Reported: ``rmse = sqrt(sum se / n)``, ``bias = sum e / n``, ``mae = sum ae / n``, ``acc = sum acc_b / n_acc``,
+``activity = sqrt(sum ff / sum tt)`` (the ratio of forecast to truth anomaly amplitude; it falls below 1 as a forecast
+blurs) and ``count = n``.  Without a climatology ``acc`` and ``activity`` are NaN and no third tensor is read.
+Non-finite values in ``f`` or ``t`` are NOT masked: they propagate into the scores of their (lead, channel).
+
+One launch pair per ``update`` (``csrc/verify.hip``) reads the two (three) tensors once - 8 (12) bytes per cell - and
+adds to one row of numbers kept on the device; ``result`` reads them once, after at most one all-reduce.
+
+No CPU fallback: ``update`` needs tensors on the HIP device.  The host side (argument checks, ``result``, ``table``)
+works on any device.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import dptr, require_hip, stream_ptr
+
+ACC_FIELDS = 8          # {n, sum se, sum e, sum ae, sum acc_b, n_acc, sum ff, sum tt}
+METRICS = ("rmse", "bias", "mae", "acc", "activity")
+
+
+def _dense_state(t: torch.Tensor, what: str) -> None:
+    if t.stride(-1) != 1 or t.stride(-2) != t.shape[-1] or t.stride(-3) != t.shape[-1] * t.shape[-2]:
+        raise ValueError(f"Scorecard.update: {what} must hold dense [C, H, W] states")
+
+
+def lat_weights_from(loss) -> torch.Tensor:
+    """the latitude weights of a ``ParadisLoss`` (``loss.lat_weights_buf``), as ``Scorecard`` takes them"""
+    return loss.lat_weights_buf
+
+
+class Scorecard:
+    """Per-lead verification scores of a rollout, accumulated on the device (module docstring for the formulas).
+
+    ``names``: the chunk's channel names (``PostSpec.names``); ``lat_weights``: ``[H]`` (any shape with H entries);
+    ``climatology``: ``[K, C, H, W]`` fp32 on the device, or ``None``.  ``acc`` is the double ``[n_leads, C, 8]``
+    accumulator on ``device``.
+
+    ``update(lead, forecast, truth, clim_index=None)``: one launch pair on the current stream, no host synchronisation,
+    neither input is written; ``forecast`` / ``truth`` ``[B, C, H, W]`` fp32 with dense ``[C, H, W]`` states and any
+    batch stride (``chunk[:, slot]`` and ``truth[:, k]`` are consumed in place); ``clim_index`` ``[B]`` int32 on the
+    device (with a one-slot climatology it may be omitted).
+    ``result(sync_dist=False)``: one device read; ``{"rmse", "bias", "mae", "acc", "activity"``: numpy float64
+    ``[n_leads, C]``, ``"count"``: numpy ``[n_leads]``, ``"names"``: list``}``; leads never updated come back as NaN
+    with count 0.  With ``sync_dist=True`` and an initialised process group ``acc`` is summed over the ranks by ONE
+    all-reduce first (through the host under gloo, as ``Validator.result``).
+    ``reset()`` clears the accumulators.  ``table(result, channels=None)``: a plain-text scorecard for logs."""
+
+    def __init__(self, names: Sequence[str], lat_weights, n_leads: int, *, climatology: Optional[torch.Tensor] = None,
+                 device="cuda"):
+        self.names = [str(n) for n in names]
+        C = len(self.names)
+        if C < 1:
+            raise ValueError("Scorecard: names must list at least one channel")
+        if isinstance(n_leads, bool) or int(n_leads) != n_leads or int(n_leads) < 1:
+            raise ValueError(f"Scorecard: n_leads must be an integer >= 1, got {n_leads!r}")
+        self.n_leads = int(n_leads)
+        self.device = torch.device(device)
+        w = torch.as_tensor(lat_weights).detach().reshape(-1)
+        if w.numel() < 1 or not w.is_floating_point():
+            raise ValueError("Scorecard: lat_weights must be a floating-point vector [H]")
+        w64 = w.double().cpu()
+        if not bool(torch.isfinite(w64).all()) or bool((w64 < 0).any()) or float(w64.sum()) <= 0.0:
+            raise ValueError("Scorecard: lat_weights must be finite, >= 0 and not all zero")
+        self._wsum = float(w64.sum())                       # Z = W * sum_h w[h], in double on the host
+        with torch.inference_mode(False):
+            self.lat_w = w.to(device=self.device, dtype=torch.float32).contiguous().clone()
+            self.acc = torch.zeros(self.n_leads, C, ACC_FIELDS, dtype=torch.float64, device=self.device)
+        self.climatology = None
+        if climatology is not None:
+            cl = climatology
+            if not isinstance(cl, torch.Tensor) or cl.dim() != 4 or cl.dtype != torch.float32 or \
+                    cl.shape[0] < 1 or cl.shape[1] != C or cl.shape[2] != w.numel() or not cl.is_contiguous():
+                raise ValueError(f"Scorecard: climatology must be a contiguous float32 [K, {C}, {w.numel()}, W] tensor")
+            if cl.device != self.lat_w.device:
+                raise ValueError(f"Scorecard: climatology lives on {cl.device}, the scorecard on {self.lat_w.device}")
+            self.climatology = cl
+        self._ws: Dict[tuple, torch.Tensor] = {}      # (device, stream) -> workspace
+        self._slot0: Dict[int, torch.Tensor] = {}     # B -> zeros [B] int32: the index of a one-slot climatology
+
+    lat_weights_from = staticmethod(lat_weights_from)
+
+    def _workspace(self, device, nbytes: int) -> torch.Tensor:
+        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() * 8 < nbytes:
+            with torch.inference_mode(False):
+                ws = self._ws[key] = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.float64, device=device)
+        return ws
+
+    def _check(self, lead, forecast, truth, clim_index):
+        """argument checks of ``update``; returns (B, C, H, W)"""
+        if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < self.n_leads:
+            raise ValueError(f"Scorecard.update: lead must be an integer in [0, {self.n_leads}), got {lead!r}")
+        C, H = len(self.names), self.lat_w.numel()
+        for what, t in (("forecast", forecast), ("truth", truth)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 4:
+                raise ValueError(f"Scorecard.update: {what} must be a [B, C, H, W] tensor")
+            if t.dtype != torch.float32:
+                raise ValueError(f"Scorecard.update: {what} must be float32, got {t.dtype}")
+        B, Cf, Hf, W = forecast.shape
+        if (Cf, Hf) != (C, H) or W < 1:
+            raise ValueError(f"Scorecard.update: forecast is {tuple(forecast.shape)}; the scorecard has {C} channels "
+                             f"and {H} latitudes")
+        if truth.shape != forecast.shape:
+            raise ValueError(f"Scorecard.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
+        _dense_state(forecast, "forecast")
+        _dense_state(truth, "truth")
+        if self.climatology is None:
+            if clim_index is not None:
+                raise ValueError("Scorecard.update: clim_index given, but the scorecard has no climatology")
+        else:
+            if self.climatology.shape[3] != W:
+                raise ValueError(f"Scorecard.update: forecast has {W} longitudes, the climatology "
+                                 f"{self.climatology.shape[3]}")
+            if clim_index is None:
+                if self.climatology.shape[0] != 1:
+                    raise ValueError(f"Scorecard.update: clim_index is needed to choose among the "
+                                     f"{self.climatology.shape[0]} climatology slots")
+            elif not isinstance(clim_index, torch.Tensor) or clim_index.dtype != torch.int32 or \
+                    tuple(clim_index.shape) != (B,):
+                raise ValueError(f"Scorecard.update: clim_index must be an int32 tensor [{B}]")
+        return B, C, H, W
+
+    def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
+               clim_index: Optional[torch.Tensor] = None) -> None:
+        B, C, H, W = self._check(lead, forecast, truth, clim_index)
+        require_hip(forecast, truth, self.lat_w)
+        if B == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
+            return
+        clim = self.climatology
+        if clim is not None:
+            if clim_index is None:
+                if B not in self._slot0:
+                    with torch.inference_mode(False):
+                        self._slot0[B] = torch.zeros(B, dtype=torch.int32, device=forecast.device)
+                clim_index = self._slot0[B]
+            if not clim_index.is_cuda:
+                raise ValueError("Scorecard.update: clim_index must live on the device")
+            clim_index = clim_index.contiguous()         # a column of [B, n_stored] becomes dense; no host wait
+        P = H * W
+
+        def bs(t):
+            return t.stride(0) if B > 1 else C * P
+
+        with_clim = clim is not None
+        ws = self._workspace(forecast.device, int(_lib.lib.paradis_verify_ws_bytes(B, C, H, W, int(with_clim))))
+        _lib.call("verify_update", (12.0 if with_clim else 8.0) * B * C * P, dptr(forecast), bs(forecast), dptr(truth),
+                  bs(truth), dptr(clim), dptr(clim_index) if with_clim else None, clim.shape[0] if with_clim else 0,
+                  dptr(self.lat_w), float(W) * self._wsum, dptr(self.acc[int(lead)]), dptr(ws), B, C, H, W,
+                  stream_ptr())
+
+    def reset(self) -> None:
+        self.acc.zero_()
+
+    def result(self, sync_dist: bool = False) -> dict:
+        import torch.distributed as dist
+        acc = self.acc
+        if sync_dist and dist.is_available() and dist.is_initialized():
+            acc = acc.clone()
+            if dist.get_backend() == "gloo":
+                acc = acc.cpu()                  # the one device-to-host read, in front of the host-side sum
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+        a = acc.cpu().numpy()
+        n, n_acc = a[..., 0], a[..., 5]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            res = {"rmse": np.sqrt(a[..., 1] / n), "bias": a[..., 2] / n, "mae": a[..., 3] / n}
+            if self.climatology is None:
+                res["acc"] = np.full(n.shape, np.nan)
+                res["activity"] = np.full(n.shape, np.nan)
+            else:
+                res["acc"] = a[..., 4] / n_acc
+                res["activity"] = np.sqrt(a[..., 6] / a[..., 7])
+        for k in METRICS:
+            res[k] = np.where(n > 0, res[k], np.nan)        # leads never updated
+        res["count"] = n[:, 0].copy()
+        res["names"] = list(self.names)
+        return res
+
+    @staticmethod
+    def table(result: dict, channels: Optional[Sequence[str]] = None) -> str:
+        """plain text, one block per metric: a row per lead, a column per channel (``channels``: a subset, by name)"""
+        names: List[str] = list(result["names"])
+        chosen = names if channels is None else [str(c) for c in channels]
+        for c in chosen:
+            if c not in names:
+                raise ValueError(f"Scorecard.table: channel '{c}' is not among the scorecard's names")
+        cols = [names.index(c) for c in chosen]
+        width = max([12] + [len(c) + 1 for c in chosen])
+        lines = []
+        for metric in METRICS:
+            lines.append(f"{metric:<6}{'count':>8}" + "".join(f"{c:>{width}}" for c in chosen))
+            for lead in range(result[metric].shape[0]):
+                vals = "".join(f"{result[metric][lead, c]:>{width}.4e}" for c in cols)
+                lines.append(f"{lead:<6d}{int(result['count'][lead]):>8d}" + vals)
+            lines.append("")
+        return "\n".join(lines[:-1])
