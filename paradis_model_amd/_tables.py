@@ -1,0 +1,88 @@
+"""Host side of the table-driven launches (``csrc/stream_common.h``): the chunk list of a tensor list, the address
+table that reaches the device through a pinned staging row, the per-stream workspace cache and the dense-state check
+of the plane kernels.  The pinned-row protocol lives here once: ``optim.AdamW``, ``optim.Muon``, ``clip.ClipPlan`` and
+``diagnostics.StatsPlan`` all go through ``AddressTable``."""
+from __future__ import annotations
+
+from typing import Dict, List, Sequence, Tuple
+
+import torch
+
+
+def chunk_list(numels: Sequence[int], chunk: int, tensors=None) -> Tuple[List[int], List[int]]:
+    """(chunk_tensor, chunk_off) as Python lists: one entry per ``chunk`` elements of every tensor, in tensor order
+    (``tensors``: the indices to walk, default all), then by offset"""
+    ct: List[int] = []
+    co: List[int] = []
+    for t in (range(len(numels)) if tensors is None else tensors):
+        for off in range(0, int(numels[t]), chunk):
+            ct.append(t)
+            co.append(off)
+    return ct, co
+
+
+class AddressTable:
+    """``rows`` rows of ``T`` int64 device addresses: ``host`` the pinned staging row, ``ptrs`` the device row the kernels
+    read (row r of tensor t at ``ptrs[r * T + t]``), ``pending`` the event of the last asynchronous copy out of ``host``.
+
+    The addresses change behind the same parameter ids (``zero_grad(set_to_none=True)``, ``load_state_dict``,
+    ``model.to()``), so ``write`` rewrites all of them before every launch; nothing waits for the device."""
+
+    def __init__(self, rows: int, T: int, device):
+        n = max(1, rows * T)
+        with torch.inference_mode(False):
+            self.host = torch.zeros(n, dtype=torch.int64).pin_memory()
+            self.ptrs = torch.zeros(n, dtype=torch.int64, device=device)
+        self.n = rows * T
+        self.pending = None
+
+    def write(self, addresses: Sequence[int]) -> bool:
+        """stage ``addresses`` (all rows, concatenated) and queue their copy to the device on the current stream; returns
+        whether the stream is capturing (the copy is then a graph node that re-reads ``host`` on every replay)"""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self.pending is not None and not capturing:       # the previous call's async copy out of `host` (long done)
+            self.pending.synchronize()
+        if self.n:
+            self.host.copy_(torch.tensor(addresses, dtype=torch.int64))
+            self.ptrs.copy_(self.host, non_blocking=True)
+            if capturing:
+                self.pending = None      # (inside a capture the copy is a graph node; nothing to wait for on the host)
+            else:
+                ev = torch.cuda.Event()
+                ev.record()
+                self.pending = ev
+        return capturing
+
+    # ------------------------------------------------------------------ HIP graphs (harness.GraphedTrainStep.eager_step)
+    def snapshot(self) -> torch.Tensor:
+        """a copy of the pinned row (a captured copy node re-reads the row on every replay)"""
+        return self.host.clone()
+
+    def restore(self, table) -> None:
+        if table is None or self.host.numel() != table.numel():
+            return
+        if self.pending is not None:
+            self.pending.synchronize()
+        self.host.copy_(table)
+
+
+def workspace(cache: Dict[tuple, torch.Tensor], device, nbytes: int) -> torch.Tensor:
+    """at least ``nbytes`` of device memory out of the owner's ``cache``, one buffer per (device, current stream): the
+    launches of one stream are ordered, so they may share it; it grows when a call needs more"""
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        with torch.inference_mode(False):
+            ws = cache[key] = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.float64, device=device)
+    return ws
+
+
+def dense_state(t: torch.Tensor, what: str, who: str, fp32: bool = False) -> None:
+    """``t[..., C, H, W]`` holds dense ``[C, H, W]`` states (any stride in front of them); ``fp32``: and is float32.
+    ``who`` / ``what`` name the caller and the argument in the error."""
+    dense = t.stride(-1) == 1 and t.stride(-2) == t.shape[-1] and t.stride(-3) == t.shape[-1] * t.shape[-2]
+    if fp32:
+        if t.dtype != torch.float32 or not dense:
+            raise ValueError(f"{who}: {what} must be float32 with dense [C, H, W] states")
+    elif not dense:
+        raise ValueError(f"{who}: {what} must hold dense [C, H, W] states")

@@ -11,7 +11,7 @@ back to ``torch.optim.AdamW`` there).
 from __future__ import annotations
 
 import math
-from typing import Iterable, List, Optional, Sequence, Union
+from typing import Iterable, Optional, Sequence, Union
 
 import torch
 
@@ -30,20 +30,14 @@ class ClipPlan:
 
     def __init__(self, numels: Sequence[int], device):
         from . import _lib
+        from ._tables import AddressTable, chunk_list
         self.T = len(numels)
-        chunk = _lib.lib.paradis_clip_grad_chunk()
-        ct: List[int] = []
-        co: List[int] = []
-        for t, n in enumerate(numels):
-            for off in range(0, int(n), chunk):
-                ct.append(t)
-                co.append(off)
+        ct, co = chunk_list(numels, _lib.lib.paradis_clip_grad_chunk())
         self.n_chunks = len(ct)
         self.numel_host = [int(n) for n in numels]
         self.n_elements = sum(self.numel_host)
+        self.addr = AddressTable(1, self.T, device)
         with torch.inference_mode(False):
-            self.host = torch.zeros(max(1, self.T), dtype=torch.int64).pin_memory()
-            self.ptrs = torch.zeros(max(1, self.T), dtype=torch.int64, device=device)
             self.numel = torch.tensor([int(n) for n in numels] or [0], dtype=torch.int64, device=device)
             self.chunk_tensor = torch.tensor(ct or [0], dtype=torch.int32, device=device)
             self.chunk_off = torch.tensor(co or [0], dtype=torch.int64, device=device)
@@ -51,7 +45,6 @@ class ClipPlan:
             self.ws = torch.empty(max(1, ws // 8), dtype=torch.float64, device=device)
             self.out = torch.zeros(2, device=device)
         _lib.require_hip(self.out)
-        self.pending = None
 
     def launch(self, grads, max_norm: float) -> torch.Tensor:
         """rewrite the address row (pinned staging buffer, non-blocking copy: the addresses change after
@@ -80,34 +73,20 @@ class ClipPlan:
             if g.numel() != numel[t]:
                 raise ValueError(f"clip_grad_norm_: a gradient of {g.numel()} elements where the plan has {numel[t]}")
             addr[t] = g.data_ptr()
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self.pending is not None and not capturing:       # the previous call's async copy out of `host` (long done)
-            self.pending.synchronize()
-        if T:
-            self.host.copy_(torch.tensor(addr, dtype=torch.int64))
-            self.ptrs.copy_(self.host, non_blocking=True)
-            if capturing:
-                self.pending = None      # (inside a capture the copy is a graph node; nothing to wait for on the host)
-            else:
-                ev = torch.cuda.Event()
-                ev.record()
-                self.pending = ev
-        _lib.call("clip_grad_norm", 12.0 * self.n_elements, dptr(self.ptrs), dptr(self.numel), dptr(self.chunk_tensor),
-                  dptr(self.chunk_off), T, self.n_chunks, max_norm, dptr(self.ws), dptr(self.out), stream_ptr())
+        self.addr.write(addr)
+        _lib.call("clip_grad_norm", 12.0 * self.n_elements, dptr(self.addr.ptrs), dptr(self.numel),
+                  dptr(self.chunk_tensor), dptr(self.chunk_off), T, self.n_chunks, max_norm, dptr(self.ws),
+                  dptr(self.out), stream_ptr())
         return self.out
 
     # ------------------------------------------------------------------ the pinned address row and HIP graphs
     def snapshot_pointer_tables(self):
         """a copy of the pinned address row (``harness.GraphedTrainStep``: the captured copy node re-reads it on every
         replay)"""
-        return self.host.clone()
+        return self.addr.snapshot()
 
     def restore_pointer_tables(self, table) -> None:
-        if table is None or self.host.numel() != table.numel():
-            return
-        if self.pending is not None:
-            self.pending.synchronize()
-        self.host.copy_(table)
+        self.addr.restore(table)
 
 
 _PLANS: dict = {}          # parameter-list key -> ClipPlan, most recently used last

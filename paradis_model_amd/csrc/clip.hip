@@ -3,18 +3,17 @@
 // optimiser step (train.py:52-53, algorithm "norm") - in three launches (ATen's foreach path: 18 device activities over the
 // default model's 335 gradients, measured), and with fewer roundings: the sum of squares is formed in double.
 //
-// Launch 1, clip_partial_kernel: workgroup b works on chunk b = (tensor, offset) of the table scheme of adamw_multi_kernel
-// (train.hip) and param_stats_kernel (stats.hip): at most CLIP_CHUNK elements of one gradient, read once; a gradient
-// address of 0 means "absent".  Thread t adds cells 4 (256 i + t) .. + 3, i = 0 .., in that order, in DOUBLE: the product
-// of two fp32 values is exact in fp64, so only the additions round.  One 16-byte load per quad where the chunk start is
-// 16-byte aligned, four scalar loads otherwise (DDP's bucket views are often only 4-byte aligned): the same bits either
-// way.  Waves by shuffles, the four waves through LDS, one ordinary store per workgroup: partial[b].
+// Layout, thread order, chunk table and block fold: stream_common.h.  What is particular here:
+// Launch 1, clip_partial_kernel: one sum per chunk, the squares of one gradient, in DOUBLE from the first product on (the
+// product of two fp32 values is exact in fp64, so only the additions round); a gradient address of 0 means "absent":
+// partial[b] = 0.
 // Launch 2, clip_finish_kernel: one workgroup; thread t adds partial[t], partial[t + 1024], .. in double, the shuffle tree,
-// the 16 wave sums in wave order; out = {(float)sqrt(S), the clip coefficient}.  No atomics: bit-identical run to run.
+// the 16 wave sums in wave order; out = {(float)sqrt(S), the clip coefficient}.
 // Launch 3, clip_scale_kernel: the chunks of launch 1 again; g *= out[1], one fp32 multiply per element; a coefficient of
 // exactly 1.0f returns at once (g * 1.0f is the same bits, NaN payloads aside, and a NaN norm gives a NaN coefficient).
 // Algorithmic HBM bytes: 4 per element (norm pass) + 8 per element (scale pass, when it clips).
 #include "common.h"
+#include "stream_common.h"
 
 #include <cmath>
 
@@ -22,74 +21,38 @@
 
 namespace {
 
-constexpr int CLIP_CHUNK = 32768;                        // elements of one tensor per workgroup: 32 quads per thread
-constexpr int CLIP_ITERS = CLIP_CHUNK / (256 * 4);
 constexpr int CLIP_FIN_THREADS = 1024, CLIP_FIN_WAVES = CLIP_FIN_THREADS / 64;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// chunk b of the table: its first element (nullptr: nothing to do) and its length n; a bad table entry and an absent
-// gradient give nothing (workgroup-uniform)
-__device__ __forceinline__ float* clip_chunk(const int64_t* __restrict__ grads, const int64_t* __restrict__ numel,
-                                             const int* __restrict__ chunk_tensor, const int64_t* __restrict__ chunk_off,
-                                             int T, int& n) {
-  const int t = chunk_tensor[blockIdx.x];
-  const int64_t off = chunk_off[blockIdx.x];
-  const int64_t left = (t >= 0 && t < T && off >= 0) ? numel[t] - off : 0;
-  n = (int)(left < (int64_t)CLIP_CHUNK ? (left > 0 ? left : 0) : (int64_t)CLIP_CHUNK);
-  if (n == 0) return nullptr;
-  const int64_t ga = grads[t];
+// the gradient's part of chunk c (nullptr, and c.n = 0, for an absent gradient)
+__device__ __forceinline__ float* clip_chunk(const int64_t* __restrict__ grads, TableChunk& c) {
+  if (c.n == 0) return nullptr;
+  const int64_t ga = grads[c.t];
   if (ga == 0) {
-    n = 0;
+    c.n = 0;
     return nullptr;
   }
-  return reinterpret_cast<float*>(ga) + off;
-}
-
-// VEC: the quad is whole and 16-byte aligned
-template <bool VEC>
-__device__ __forceinline__ double sum_squares(const float* __restrict__ g, int first, int last, int n, double s) {
-  // (the loop vectorizer would interleave two iterations and break the 16-byte accesses into 4-byte ones)
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-  for (int i = first; i < last; ++i) {
-    const int q0 = 4 * (256 * i + (int)threadIdx.x);
-    if (q0 >= n) break;
-    float v[4];
-    if (VEC) {
-      const float4 q = *reinterpret_cast<const float4*>(g + q0);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      // cells past the end are +0: a sum that starts at +0 is never -0, so adding them changes no bit
-#pragma unroll
-      for (int k = 0; k < 4; ++k) v[k] = q0 + k < n ? g[q0 + k] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s += (double)v[k] * (double)v[k];
-  }
-  return s;
+  return reinterpret_cast<float*>(ga) + c.off;
 }
 
 __global__ void __launch_bounds__(256)
 clip_partial_kernel(const int64_t* __restrict__ grads, const int64_t* __restrict__ numel,
                     const int* __restrict__ chunk_tensor, const int64_t* __restrict__ chunk_off, int T,
                     double* __restrict__ partial /* [n_chunks] */) {
-  __shared__ double red[4];
-  int n;
-  const float* g = clip_chunk(grads, numel, chunk_tensor, chunk_off, T, n);
-  double s = 0.0;
+  TableChunk c = table_chunk(numel, chunk_tensor, chunk_off, T);
+  const float* __restrict__ g = clip_chunk(grads, c);
+  const int n = c.n;
+  double s[1] = {0.0};
   if (n > 0) {       // (workgroup-uniform)
-    const int whole = aligned16(g) ? n / 1024 : 0;      // iterations whose 256 quads are all whole: 1024 cells each
-    s = sum_squares<true>(g, 0, whole, n, s);
-    s = sum_squares<false>(g, whole, CLIP_ITERS, n, s);
+    s[0] = walk_chunk(aligned16(g), n, 0.0, [&](auto vec, double a, int q0) {
+      float v[4];
+      load_quad<decltype(vec)::value>(g, q0, n, v);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a += (double)v[k] * (double)v[k];
+      return a;
+    });
   }
-  s = wave_sum_f64(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s[0] = wave_sum_f64(s[0]);
+  block_fold4(s, [&](int, double v) { partial[blockIdx.x] = v; });
 }
 
 __global__ void __launch_bounds__(CLIP_FIN_THREADS)
@@ -110,42 +73,33 @@ clip_finish_kernel(const double* __restrict__ partial, int n_chunks, double max_
   }
 }
 
-template <bool VEC>
-__device__ __forceinline__ void scale_quads(float* __restrict__ g, int first, int last, int n, float c) {
-  // (the loop vectorizer would interleave two iterations and break the 16-byte accesses into 4-byte ones)
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(4)
-  for (int i = first; i < last; ++i) {
-    const int q0 = 4 * (256 * i + (int)threadIdx.x);
-    if (q0 >= n) break;
-    if (VEC) {
-      float4 q = *reinterpret_cast<const float4*>(g + q0);
-      q.x *= c; q.y *= c; q.z *= c; q.w *= c;
-      *reinterpret_cast<float4*>(g + q0) = q;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (q0 + k < n) g[q0 + k] *= c;
-    }
-  }
-}
-
 __global__ void __launch_bounds__(256)
 clip_scale_kernel(const int64_t* __restrict__ grads, const int64_t* __restrict__ numel,
                   const int* __restrict__ chunk_tensor, const int64_t* __restrict__ chunk_off, int T,
                   const float* __restrict__ out) {
-  const float c = out[1];
-  if (c == 1.0f) return;       // (workgroup-uniform) nothing to clip: g * 1.0f is g
-  int n;
-  float* g = clip_chunk(grads, numel, chunk_tensor, chunk_off, T, n);
+  const float coef = out[1];
+  if (coef == 1.0f) return;       // (workgroup-uniform) nothing to clip: g * 1.0f is g
+  TableChunk c = table_chunk(numel, chunk_tensor, chunk_off, T);
+  float* g = clip_chunk(grads, c);
+  const int n = c.n;
   if (n == 0) return;
-  const int whole = aligned16(g) ? n / 1024 : 0;
-  scale_quads<true>(g, 0, whole, n, c);
-  scale_quads<false>(g, whole, CLIP_ITERS, n, c);
+  walk_chunk(aligned16(g), n, NoSums{}, [&](auto vec, NoSums a, int q0) {
+    if (decltype(vec)::value) {
+      float4 q = *reinterpret_cast<const float4*>(g + q0);
+      q.x *= coef; q.y *= coef; q.z *= coef; q.w *= coef;
+      *reinterpret_cast<float4*>(g + q0) = q;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (q0 + k < n) g[q0 + k] *= coef;
+    }
+    return a;
+  });
 }
 
 }  // namespace
 
-extern "C" int paradis_clip_grad_chunk(void) { return CLIP_CHUNK; }
+extern "C" int paradis_clip_grad_chunk(void) { return TABLE_CHUNK; }
 
 // the partials [n_chunks] in double
 extern "C" size_t paradis_clip_grad_ws_bytes(int n_chunks) {

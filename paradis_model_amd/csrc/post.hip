@@ -203,9 +203,8 @@ extern "C" int paradis_forecast_post(const float* output, int64_t out_bs, float*
   a.in_bs = out_bs; a.out_bs = chunk_bs; a.dew_bs = dew_bs;
   a.eps_q = eps_q;
   a.n_units = n_units; a.B = B; a.H = H; a.W = W;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  const bool vec = (W % 4 == 0) && al16(a.in) && al16(a.out) && (out_bs % 4 == 0) && (chunk_bs % 4 == 0) &&
-                   (a.dew == nullptr || (al16(a.dew) && dew_bs % 4 == 0));
+  const bool vec = (W % 4 == 0) && aligned16(a.in) && aligned16(a.out) && (out_bs % 4 == 0) && (chunk_bs % 4 == 0) &&
+                   (a.dew == nullptr || (aligned16(a.dew) && dew_bs % 4 == 0));
   const int64_t total = (int64_t)B * n_units * H * (vec ? W / 4 : W);
   const unsigned blocks = (unsigned)(ceil_div64(total, 256) < 2048 ? ceil_div64(total, 256) : 2048);
   if (vec) hipLaunchKernelGGL(forecast_post_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);

@@ -14,20 +14,17 @@
 // kind 2 ("none": the AMSE validation loss, whose value comes from paradis_amse_loss) skips s0 / s1 and writes zeros;
 // workgroups of channels without a report then read nothing.
 //
-// Work layout: a workgroup sees ONE channel - piece k of SCORE_PIECE cells of plane (b, c) - so weights, class and
-// de-normalisation constants are workgroup-uniform.  Thread t adds cells 4 (256 i + t) .. + 3 of its piece, i = 0 ..,
-// in that order, whichever way they were loaded (one 16-byte load when W % 4 == 0 and the planes are 16-byte aligned,
-// four scalar loads otherwise): both paths give the same bits.  Waves by shuffles, the four waves through LDS, three
-// ordinary stores per workgroup; no atomics: bitwise reproducible run to run.
+// Work layout (stream_common.h; the piece loop is written out here): a workgroup sees ONE channel - piece k of plane
+// (b, c) - so weights, class and de-normalisation constants are workgroup-uniform.  The thread's and the workgroup's sums
+// stay fp32 (three ordinary stores per workgroup); the finishing kernel folds them in double.
 // Algorithmic HBM bytes: 8*B*C*H*W (the training loss kernel with its gradient store: 12).
 #include "common.h"
+#include "stream_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SCORE_PIECE = 8192;                 // cells of one plane per workgroup: 8 x 16 bytes per thread and tensor
-constexpr int SCORE_ITERS = SCORE_PIECE / (256 * 4);
 constexpr int KIND_NONE = 2;
 constexpr int CLS_Z = 1, CLS_HUM = 2, CLS_PRECIP = 3;   // codes of paradis_normalize_features
 
@@ -65,11 +62,10 @@ __device__ __forceinline__ float denorm_p(float x) { return fmaxf(expf(x - 10.0f
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) val_score_kernel(ScoreArgs a) {
-  __shared__ float red[3][4];
   const int c = blockIdx.x / a.nb;
   const int j = blockIdx.x - c * a.nb;
   const int b = j / a.npieces;
-  const int64_t start = (int64_t)(j - b * a.npieces) * SCORE_PIECE;
+  const int64_t start = (int64_t)(j - b * a.npieces) * PLANE_PIECE;
   const int cls = (a.rflag != nullptr && a.rflag[c] >= 0) ? a.rcls[c] : 0;      // 0: not a report channel
   const bool with_loss = a.kind != KIND_NONE;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
@@ -83,19 +79,17 @@ __global__ void __launch_bounds__(256) val_score_kernel(ScoreArgs a) {
       lmin = logf(a.rp0[c]);
       lspan = logf(qmax) - lmin;
     }
-    const int64_t end = min(a.P, start + SCORE_PIECE);
+    const int64_t end = min(a.P, start + PLANE_PIECE);
 #pragma unroll
-    for (int i = 0; i < SCORE_ITERS; ++i) {
+    for (int i = 0; i < PLANE_ITERS; ++i) {
       const int64_t q0 = start + 4 * (int64_t)(256 * i + (int)threadIdx.x);
       if (q0 >= end) break;
       float pv[4], tv[4];
       int hv[4];
       const int h0 = (int)(q0 / a.W);
       if (VEC) {     // W % 4 == 0, P % 4 == 0: the four cells exist and share a row
-        const float4 x = *reinterpret_cast<const float4*>(p + q0);
-        const float4 y = *reinterpret_cast<const float4*>(t + q0);
-        pv[0] = x.x; pv[1] = x.y; pv[2] = x.z; pv[3] = x.w;
-        tv[0] = y.x; tv[1] = y.y; tv[2] = y.z; tv[3] = y.w;
+        load_quad<true>(p, q0, end, pv);
+        load_quad<true>(t, q0, end, tv);
         hv[0] = hv[1] = hv[2] = hv[3] = h0;
       } else {
         const int w0 = (int)(q0 - (int64_t)h0 * a.W);
@@ -125,25 +119,8 @@ __global__ void __launch_bounds__(256) val_score_kernel(ScoreArgs a) {
       }
     }
   }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s0;
-    red[1][threadIdx.x >> 6] = s1;
-    red[2][threadIdx.x >> 6] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const float* r = red[threadIdx.x];
-    a.partial[((int64_t)threadIdx.x * a.C + c) * a.nb + j] = (r[0] + r[1]) + (r[2] + r[3]);
-  }
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  const float s[3] = {wave_sum(s0), wave_sum(s1), wave_sum(s2)};
+  block_fold4(s, [&](int i, float v) { a.partial[((int64_t)i * a.C + c) * a.nb + j] = v; });
 }
 
 // one workgroup of 16 waves; wave w owns channels w, w + 16, ..: its lanes sum the channel's nb partials in double
@@ -194,7 +171,7 @@ val_score_finish_kernel(const float* __restrict__ partial, const float* __restri
   }
 }
 
-inline int64_t score_pieces(int H, int W) { return ceil_div64((int64_t)H * W, SCORE_PIECE); }
+inline int64_t score_pieces(int H, int W) { return ceil_div64((int64_t)H * W, PLANE_PIECE); }
 
 }  // namespace
 
@@ -234,8 +211,7 @@ extern "C" int paradis_val_score(const float* pred, int64_t pred_bs, const float
   a.partial = static_cast<float*>(workspace);
   a.pred_bs = pred_bs; a.target_bs = target_bs; a.P = P;
   a.C = C; a.W = W; a.npieces = (int)npieces; a.nb = (int)nb; a.kind = kind; a.delta = delta;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  const bool vec = (W % 4 == 0) && al16(pred) && al16(target) && (pred_bs % 4 == 0) && (target_bs % 4 == 0);
+  const bool vec = (W % 4 == 0) && aligned16(pred) && aligned16(target) && (pred_bs % 4 == 0) && (target_bs % 4 == 0);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)(nb * C));
   if (vec) hipLaunchKernelGGL(val_score_kernel<true>, grid, dim3(256), 0, st, a);

@@ -3,48 +3,28 @@
 // the gradient . moment dot product, in ONE streaming read of all tensors instead of up to four ATen reductions and four
 // scalar adds per tensor (335 tensors in the default model).
 //
-// Launch 1, param_stats_kernel: workgroup b works on chunk b = (tensor, offset) of the table scheme of
-// adamw_multi_kernel (train.hip): at most STATS_CHUNK elements of p, g and m, read once.  Address rows: parameter,
-// gradient, first moment; a gradient or moment address of 0 means "absent" (the moment of a parameter without a gradient
-// is skipped, as the reference skips it).  Thread t adds cells 4 (256 i + t) .. + 3, i = 0 .., in that order, in DOUBLE:
-// the product of two fp32 values is exact in fp64, so only the additions round.  One 16-byte load per tensor and quad when
-// every present tensor's chunk start is 16-byte aligned, four scalar loads otherwise: the same bits either way.  Waves
-// by shuffles, the four waves through LDS, four ordinary stores per workgroup: partial[b] = {Sp2, Sg2, Sgm, Sm2}.
+// Layout, thread order, chunk table and block fold: stream_common.h.  What is particular here:
+// Launch 1, param_stats_kernel: address rows parameter, gradient, first moment; a gradient or moment address of 0 means
+// "absent" (the moment of a parameter without a gradient is skipped, as the reference skips it).  Four sums per chunk, in
+// DOUBLE from the first product on (the product of two fp32 values is exact in fp64, so only the additions round):
+// partial[b] = {Sp2, Sg2, Sgm, Sm2}.  16-byte loads when every present tensor's chunk start is 16-byte aligned.
 // Launch 2, param_stats_finish_kernel: one workgroup; the chunk table is sorted by group, group_first_chunk[G + 1]
 // delimits each group's chunks; a wave sums its group's partials in double (lane-strided by index, then the shuffle
-// tree), the totals are the sum of the group sums in group order.  No atomics: bitwise reproducible run to run.
+// tree), the totals are the sum of the group sums in group order.
 // Algorithmic HBM bytes: 12 per element where all three tensors are present.
 #include "common.h"
+#include "stream_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int STATS_CHUNK = 32768;                       // elements of one tensor per workgroup: 32 quads per thread
-constexpr int STATS_ITERS = STATS_CHUNK / (256 * 4);
 constexpr int STATS_FIN_THREADS = 1024, STATS_FIN_WAVES = STATS_FIN_THREADS / 64;
 constexpr int STATS_MAX_GROUPS = 1024;                   // group sums of the finishing kernel live in LDS (32 KB)
 constexpr int STATS_COLS = 8;                            // out row: Sp2, Sg2, Sgm, Sm2, grad norm, gradratio, pnorm, alignment
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// four cells of x starting at q0 (chunk-relative), zeros past n; VEC: the quad is whole and 16-byte aligned
-template <bool VEC>
-__device__ __forceinline__ void load_quad(const float* __restrict__ x, int q0, int n, float (&v)[4]) {
-  if (VEC) {
-    const float4 q = *reinterpret_cast<const float4*>(x + q0);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = q0 + k < n ? x[q0 + k] : 0.f;
-  }
-}
-
-// cells past the end are +0: a sum that starts at +0 is never -0, so adding them changes no bit
+// iterations [first, last) of the chunk walk (stream_common.h), three tensors at once; its own loop: under the
+// pragmas of walk_chunk_iters this kernel compiles to other code (50 VGPRs for 102, other loads)
 template <bool VEC>
 __device__ __forceinline__ void add_quads(const float* __restrict__ p, const float* __restrict__ g,
                                           const float* __restrict__ m, int first, int last, int n, double (&s)[4]) {
@@ -72,34 +52,23 @@ __global__ void __launch_bounds__(256)
 param_stats_kernel(const int64_t* __restrict__ ptrs /* [3][T]: p, g, m */, const int64_t* __restrict__ numel,
                    const int* __restrict__ chunk_tensor, const int64_t* __restrict__ chunk_off, int T,
                    double* __restrict__ partial /* [n_chunks][4] */) {
-  __shared__ double red[4][4];
   double s[4] = {0.0, 0.0, 0.0, 0.0};
-  const int t = chunk_tensor[blockIdx.x];
-  const int64_t off = chunk_off[blockIdx.x];
-  const int64_t left = (t >= 0 && t < T && off >= 0) ? numel[t] - off : 0;     // a bad table entry reads nothing
-  const int n = (int)(left < (int64_t)STATS_CHUNK ? (left > 0 ? left : 0) : (int64_t)STATS_CHUNK);
+  const TableChunk c = table_chunk(numel, chunk_tensor, chunk_off, T);
+  const int n = c.n;
   if (n > 0) {       // (workgroup-uniform)
-    const float* p = reinterpret_cast<const float*>(ptrs[t]) + off;
-    const int64_t ga = ptrs[T + t], ma = ptrs[2 * T + t];
-    const float* g = ga != 0 ? reinterpret_cast<const float*>(ga) + off : nullptr;
-    const float* m = (ga != 0 && ma != 0) ? reinterpret_cast<const float*>(ma) + off : nullptr;
+    const float* p = reinterpret_cast<const float*>(ptrs[c.t]) + c.off;
+    const int64_t ga = ptrs[T + c.t], ma = ptrs[2 * T + c.t];
+    const float* g = ga != 0 ? reinterpret_cast<const float*>(ga) + c.off : nullptr;
+    const float* m = (ga != 0 && ma != 0) ? reinterpret_cast<const float*>(ma) + c.off : nullptr;
     const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m)) & 15u) == 0;
     // iterations whose 256 quads are all whole: 1024 cells each
     const int whole = vec ? n / 1024 : 0;
     add_quads<true>(p, g, m, 0, whole, n, s);
-    add_quads<false>(p, g, m, whole, STATS_ITERS, n, s);
+    add_quads<false>(p, g, m, whole, TABLE_ITERS, n, s);
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) s[j] = wave_sum_f64(s[j]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[j][threadIdx.x >> 6] = s[j];
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const double* r = red[threadIdx.x];
-    partial[(int64_t)blockIdx.x * 4 + threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
-  }
+  block_fold4(s, [&](int j, double v) { partial[(int64_t)blockIdx.x * 4 + j] = v; });
 }
 
 __device__ __forceinline__ void write_row(float* __restrict__ o, const double (&a)[4]) {
@@ -146,7 +115,7 @@ param_stats_finish_kernel(const double* __restrict__ partial, const int* __restr
 
 }  // namespace
 
-extern "C" int paradis_param_stats_chunk(void) { return STATS_CHUNK; }
+extern "C" int paradis_param_stats_chunk(void) { return TABLE_CHUNK; }
 
 // the partials [n_chunks][4] in double
 extern "C" size_t paradis_param_stats_ws_bytes(int n_chunks) {

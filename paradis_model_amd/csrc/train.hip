@@ -6,6 +6,7 @@
 // All HBM-bound streaming kernels.
 #include <algorithm>
 #include "common.h"
+#include "stream_common.h"
 
 namespace {
 
@@ -53,8 +54,7 @@ loss_finish_kernel(const float* __restrict__ partial, float* __restrict__ out, i
   __shared__ double red[4];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) acc += (double)partial[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum_f64(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) out[0] = (float)((red[0] + red[1] + red[2] + red[3]) * (double)inv_n);
@@ -121,8 +121,7 @@ adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restri
 
 // One launch for a whole parameter group: block c works on chunk c = (tensor index, offset); all
 // tensors share the hyper-parameters and the step count.  (335 per-tensor launches of ~5 us are
-// launch-bound: 0.7 % of the training step.)
-constexpr int ADAMW_CHUNK = 32768;
+// launch-bound: 0.7 % of the training step.)  The chunk table: stream_common.h.
 // dev (optional): {int32 step at [0], the bits of the fp32 lr at [1]} kept on the device so
 // that a captured HIP graph of the training step stays valid from one replay to the next (the host-side step
 // count and learning rate would be frozen into the kernel arguments): the coefficients that depend on them are then
@@ -148,14 +147,13 @@ adamw_multi_kernel(const int64_t* __restrict__ ptrs /* [4][T]: p, g, m, v */, co
     k.step_size = co[1];
     k.bc2_sqrt = co[2];
   }
-  const int t = chunk_tensor[blockIdx.x];
-  const int64_t off = chunk_off[blockIdx.x];
-  const int64_t n = min((int64_t)ADAMW_CHUNK, numel[t] - off);
-  float* p = reinterpret_cast<float*>(ptrs[t]) + off;
-  const float* g = reinterpret_cast<const float*>(ptrs[T + t]) + off;
-  float* m = reinterpret_cast<float*>(ptrs[2 * T + t]) + off;
-  float* v = reinterpret_cast<float*>(ptrs[3 * T + t]) + off;
-  for (int64_t i = threadIdx.x; i < n; i += 256) adamw_update(p, g, m, v, i, k);
+  const TableChunk c = table_chunk(numel, chunk_tensor, chunk_off, T);
+  if (c.n == 0) return;       // (workgroup-uniform) a bad table entry touches nothing
+  float* p = reinterpret_cast<float*>(ptrs[c.t]) + c.off;
+  const float* g = reinterpret_cast<const float*>(ptrs[T + c.t]) + c.off;
+  float* m = reinterpret_cast<float*>(ptrs[2 * T + c.t]) + c.off;
+  float* v = reinterpret_cast<float*>(ptrs[3 * T + c.t]) + c.off;
+  for (int64_t i = threadIdx.x; i < c.n; i += 256) adamw_update(p, g, m, v, i, k);
 }
 
 __global__ void adamw_tick_kernel(int* __restrict__ dev) { dev[0] += 1; }
@@ -215,7 +213,7 @@ extern "C" int paradis_copy_channels(const float* src, int64_t src_bs, float* ds
   return 0;
 }
 
-extern "C" int paradis_adamw_chunk(void) { return ADAMW_CHUNK; }
+extern "C" int paradis_adamw_chunk(void) { return TABLE_CHUNK; }
 
 extern "C" int paradis_adamw_multi_d(const int64_t* ptrs, const int64_t* numel, const int* chunk_tensor,
                                      const int64_t* chunk_off, int n_tensors, int n_chunks, double lr,

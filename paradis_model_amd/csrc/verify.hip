@@ -9,15 +9,13 @@
 // Without a climatology only s0 .. s2 exist, no third tensor is read and acc[c][4 .. 7] are not touched.
 // Non-finite values are not masked: they propagate into every sum of their plane.
 //
-// Work layout (score.hip's): a workgroup sees ONE plane - piece j of VERIFY_PIECE cells of plane (b, c) - so clim_index[b]
-// and the three plane bases are workgroup-uniform.  Thread t adds cells 4 (256 i + t) .. + 3 of its piece, i = 0 .., in
-// that order, whichever way they were loaded (one 16-byte load per tensor when W % 4 == 0 and all plane bases are 16-byte
-// aligned, four scalar loads otherwise): both paths give the same bits.  A quad may straddle a latitude row when
-// W % 4 != 0: the row of a cell is cell / W, per cell.  The thread's sums are fp32 over its at most VERIFY_PIECE / 256 = 32
-// cells; they are widened to double before the wave shuffles, the LDS step across the four waves and the store
-// (partial [6 or 3][B C][npieces], ordinary stores).  No atomics anywhere: the accumulators are bit-identical run to run.
+// Work layout (stream_common.h; the piece loop is written out here): a workgroup sees ONE plane - piece j of plane
+// (b, c) - so clim_index[b] and the three plane bases are workgroup-uniform.  The thread's sums are fp32 over its at most
+// PLANE_PIECE / 256 = 32 cells; they are widened to double before the wave shuffles, the LDS step across the four waves
+// and the store (partial [6 or 3][B C][npieces]).
 // Algorithmic HBM bytes: 12*B*C*H*W with a climatology, 8*B*C*H*W without.
 #include "common.h"
+#include "stream_common.h"
 
 #include <cmath>
 
@@ -25,8 +23,6 @@
 
 namespace {
 
-constexpr int VERIFY_PIECE = 8192;                // cells of one plane per workgroup: 8 x 16 bytes per thread and tensor
-constexpr int VERIFY_ITERS = VERIFY_PIECE / (256 * 4);
 constexpr int VERIFY_ACC = 8;                     // doubles per (lead, channel)
 
 constexpr int verify_sums(bool clim) { return clim ? 6 : 3; }
@@ -44,12 +40,6 @@ struct VerifyArgs {
   int64_t planes;           // B C
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // cells [start, end) of one plane; VEC: every quad is whole, 16-byte aligned and inside one row
 template <bool CLIM, bool VEC>
 __device__ __forceinline__ void verify_piece_sums(const float* __restrict__ f, const float* __restrict__ t,
@@ -57,20 +47,15 @@ __device__ __forceinline__ void verify_piece_sums(const float* __restrict__ f, c
                                                   int start, int end, float (&s)[6]) {
   // (the loop vectorizer would interleave two iterations and break the 16-byte accesses into 4-byte ones)
 #pragma clang loop vectorize(disable) interleave(disable) unroll(full)
-  for (int i = 0; i < VERIFY_ITERS; ++i) {
+  for (int i = 0; i < PLANE_ITERS; ++i) {
     const int q0 = start + 4 * (256 * i + (int)threadIdx.x);
     if (q0 >= end) break;
     float fv[4], tv[4], cv[4] = {0.f, 0.f, 0.f, 0.f}, wv[4];
     const int h0 = q0 / W;
     if (VEC) {
-      const float4 x = *reinterpret_cast<const float4*>(f + q0);
-      const float4 y = *reinterpret_cast<const float4*>(t + q0);
-      fv[0] = x.x; fv[1] = x.y; fv[2] = x.z; fv[3] = x.w;
-      tv[0] = y.x; tv[1] = y.y; tv[2] = y.z; tv[3] = y.w;
-      if (CLIM) {
-        const float4 z = *reinterpret_cast<const float4*>(cl + q0);
-        cv[0] = z.x; cv[1] = z.y; cv[2] = z.z; cv[3] = z.w;
-      }
+      load_quad<true>(f, q0, end, fv);
+      load_quad<true>(t, q0, end, tv);
+      if (CLIM) load_quad<true>(cl, q0, end, cv);
       wv[0] = wv[1] = wv[2] = wv[3] = lat_w[h0];
     } else {
       const int w0 = q0 - h0 * W;
@@ -104,7 +89,6 @@ __device__ __forceinline__ void verify_piece_sums(const float* __restrict__ f, c
 template <bool CLIM>
 __global__ void __launch_bounds__(256) verify_kernel(VerifyArgs a) {
   constexpr int NS = verify_sums(CLIM);
-  __shared__ double red[NS][4];
   const int64_t plane = blockIdx.x / a.npieces;                      // b C + c
   const int piece = (int)(blockIdx.x - plane * a.npieces);
   const int b = (int)(plane / a.C), c = (int)(plane - (int64_t)b * a.C);
@@ -119,22 +103,17 @@ __global__ void __launch_bounds__(256) verify_kernel(VerifyArgs a) {
   }
   float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (!bad_slot) {
-    const int start = piece * VERIFY_PIECE;                          // P < 2^31
-    const int end = (int)min(a.P, (int64_t)start + VERIFY_PIECE);
+    const int start = piece * PLANE_PIECE;                           // P < 2^31
+    const int end = (int)min(a.P, (int64_t)start + PLANE_PIECE);
     if (a.vec) verify_piece_sums<CLIM, true>(f, t, cl, a.lat_w, a.W, start, end, s);
     else verify_piece_sums<CLIM, false>(f, t, cl, a.lat_w, a.W, start, end, s);
   }
+  double sd[NS];
 #pragma unroll
-  for (int i = 0; i < NS; ++i) {
-    const double v = wave_sum_f64((double)s[i]);
-    if ((threadIdx.x & 63) == 0) red[i][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    const double* r = red[threadIdx.x];
-    const double v = (r[0] + r[1]) + (r[2] + r[3]);
-    a.partial[((int64_t)threadIdx.x * a.planes + plane) * a.npieces + piece] = bad_slot ? (double)NAN : v;
-  }
+  for (int i = 0; i < NS; ++i) sd[i] = wave_sum_f64((double)s[i]);
+  block_fold4(sd, [&](int i, double v) {
+    a.partial[((int64_t)i * a.planes + plane) * a.npieces + piece] = bad_slot ? (double)NAN : v;
+  });
 }
 
 // one workgroup (one wave) per channel; for b = 0 .. B - 1 in order: lane i < NS folds the pieces of sum i of plane
@@ -183,11 +162,11 @@ __global__ void __launch_bounds__(64) verify_finish_kernel(const double* __restr
   }
 }
 
-inline int64_t verify_pieces(int H, int W) { return ceil_div64((int64_t)H * W, VERIFY_PIECE); }
+inline int64_t verify_pieces(int H, int W) { return ceil_div64((int64_t)H * W, PLANE_PIECE); }
 
 }  // namespace
 
-extern "C" int paradis_verify_piece(void) { return VERIFY_PIECE; }
+extern "C" int paradis_verify_piece(void) { return PLANE_PIECE; }
 
 extern "C" size_t paradis_verify_ws_bytes(int B, int C, int H, int W, int with_clim) {
   if (B < 1 || C < 1 || H < 1 || W < 1) return 0;
@@ -207,7 +186,7 @@ extern "C" int paradis_verify_update(const float* fc, int64_t fc_bs, const float
   PD_REQUIRE(ws != nullptr, "verify_update: ws (workspace) missing");
   PD_REQUIRE(fc && truth && lat_w, "verify_update: null input pointer");
   const int64_t P = (int64_t)H * W;
-  PD_REQUIRE(P < (1ll << 31) - VERIFY_PIECE, "verify_update: a plane of %d x %d cells is too large", H, W);
+  PD_REQUIRE(P < (1ll << 31) - PLANE_PIECE, "verify_update: a plane of %d x %d cells is too large", H, W);
   const int64_t npieces = verify_pieces(H, W), planes = (int64_t)B * C;
   PD_REQUIRE(planes * npieces < (1ll << 31), "verify_update: %lld workgroups exceed the grid limit",
              (long long)(planes * npieces));

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
+from ._tables import AddressTable, chunk_list
 
 COLS = 8                                    # Sp2, Sg2, Sgm, Sm2, grad norm, gradratio, pnorm, alignment
 SUM_P2, SUM_G2, SUM_GM, SUM_M2, GRAD, RATIO, PNORM, ALIGN = range(COLS)
@@ -49,11 +50,9 @@ def chunk_table(numels: Sequence[int], groups: Sequence[int], n_groups: int, chu
     first = [0] * (n_groups + 1)
     for g in range(n_groups):
         first[g] = len(ct)
-        for t, (n, tg) in enumerate(zip(numels, groups)):
-            if tg == g:
-                for off in range(0, int(n), chunk):
-                    ct.append(t)
-                    co.append(off)
+        gt, go = chunk_list(numels, chunk, [t for t, tg in enumerate(groups) if tg == g])
+        ct += gt
+        co += go
     first[n_groups] = len(ct)
     return ct, co, first
 
@@ -68,9 +67,8 @@ class StatsPlan:
         chunk = _lib.lib.paradis_param_stats_chunk()
         ct, co, first = chunk_table(numels, groups, self.G, chunk)
         self.n_chunks = len(ct)
+        self.addr = AddressTable(3, self.T, device)
         with torch.inference_mode(False):
-            self.host = torch.zeros(max(1, 3 * self.T), dtype=torch.int64).pin_memory()
-            self.ptrs = torch.zeros(max(1, 3 * self.T), dtype=torch.int64, device=device)
             self.numel = torch.tensor(list(numels) or [0], dtype=torch.int64, device=device)
             self.chunk_tensor = torch.tensor(ct or [0], dtype=torch.int32, device=device)
             self.chunk_off = torch.tensor(co or [0], dtype=torch.int64, device=device)
@@ -81,7 +79,6 @@ class StatsPlan:
         if self.out.numel() != (self.G + 1) * COLS or not self.out.is_contiguous():
             raise ValueError(f"param_stats: out must be a dense [{self.G + 1}, {COLS}] tensor")
         require_hip(self.out)
-        self.pending = None
 
     def launch(self, params, grads, moments) -> torch.Tensor:
         """rewrite the address rows (pinned staging buffer, non-blocking copy) and run the launch pair on the current stream"""
@@ -103,22 +100,17 @@ class StatsPlan:
             addr[T + t] = g.data_ptr() if g is not None else 0
             addr[2 * T + t] = m.data_ptr() if (m is not None and g is not None) else 0
             nbytes += 4 * p.numel() * (1 + (g is not None) + (g is not None and m is not None))
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self.pending is not None and not capturing:       # the previous call's async copy out of `host` (long done)
-            self.pending.synchronize()
-        if T:
-            self.host.copy_(torch.tensor(addr, dtype=torch.int64))
-            self.ptrs.copy_(self.host, non_blocking=True)
-            if capturing:
-                self.pending = None      # (inside a capture the copy is a graph node; nothing to wait for on the host)
-            else:
-                ev = torch.cuda.Event()
-                ev.record()
-                self.pending = ev
-        _lib.call("param_stats", float(nbytes), dptr(self.ptrs), dptr(self.numel), dptr(self.chunk_tensor),
+        self.addr.write(addr)
+        _lib.call("param_stats", float(nbytes), dptr(self.addr.ptrs), dptr(self.numel), dptr(self.chunk_tensor),
                   dptr(self.chunk_off), dptr(self.group_first), T, self.n_chunks, self.G, dptr(self.ws), dptr(self.out),
                   stream_ptr())
         return self.out
+
+    def snapshot_pointer_tables(self):
+        return self.addr.snapshot()
+
+    def restore_pointer_tables(self, table) -> None:
+        self.addr.restore(table)
 
 
 def param_stats(params, grads, moments, groups: Sequence[int], n_groups: Optional[int] = None,
@@ -251,15 +243,11 @@ class TrainStats:
     def snapshot_pointer_tables(self):
         """a copy of the pinned address table (``harness.GraphedTrainStep``: the captured copy node re-reads it on every
         replay)"""
-        return None if self._plan is None else self._plan.host.clone()
+        return None if self._plan is None else self._plan.snapshot_pointer_tables()
 
     def restore_pointer_tables(self, table) -> None:
-        pl = self._plan
-        if table is None or pl is None or pl.host.numel() != table.numel():
-            return
-        if pl.pending is not None:
-            pl.pending.synchronize()
-        pl.host.copy_(table)
+        if self._plan is not None:
+            self._plan.restore_pointer_tables(table)
 
     # ------------------------------------------------------------------ the logged values
     def result(self, sync_dist: bool = False) -> Dict[str, float]:

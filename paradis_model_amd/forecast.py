@@ -24,6 +24,7 @@ import torch
 
 from . import _lib, harness
 from ._lib import dptr, require_hip, stream_ptr
+from ._tables import dense_state
 from .feed import KIND_HUMIDITY, KIND_PRECIP, KIND_ZSCORE
 
 UNIT_SINGLE, UNIT_LEVEL, UNIT_SURFACE = 0, 1, 2
@@ -158,12 +159,6 @@ class PostSpec:
         return self._trig[key]
 
 
-def _dense_state(t: torch.Tensor, what: str) -> None:
-    if t.dtype != torch.float32 or t.stride(-1) != 1 or t.stride(-2) != t.shape[-1] or \
-            t.stride(-3) != t.shape[-1] * t.shape[-2]:
-        raise ValueError(f"postprocess: {what} must be float32 with dense [C, H, W] states")
-
-
 def postprocess(output: torch.Tensor, spec: PostSpec, lat_deg, lon_deg, chunk: torch.Tensor, slot: int,
                 dew: Optional[torch.Tensor] = None) -> None:
     """``chunk[:, slot] = physical units of output`` (and ``dew[:, slot]`` = dew-point depression per level) by one launch
@@ -179,8 +174,8 @@ def postprocess(output: torch.Tensor, spec: PostSpec, lat_deg, lon_deg, chunk: t
     if C != spec.num_channels or tuple(chunk.shape) != (B, T, C, H, W) or not 0 <= slot < T:
         raise ValueError(f"postprocess: output {tuple(output.shape)}, chunk {tuple(chunk.shape)}, slot {slot} and a "
                          f"{spec.num_channels}-channel spec do not fit together")
-    _dense_state(output, "output")
-    _dense_state(chunk, "chunk")
+    dense_state(output, "output", "postprocess", fp32=True)
+    dense_state(chunk, "chunk", "postprocess", fp32=True)
     P = H * W
     L = spec.num_levels
     if dew is not None:
@@ -188,7 +183,7 @@ def postprocess(output: torch.Tensor, spec: PostSpec, lat_deg, lon_deg, chunk: t
             raise ValueError("postprocess: dew-point output asked from a spec built with dewpoint=False")
         if tuple(dew.shape) != (B, T, L, H, W):
             raise ValueError(f"postprocess: dew must be {(B, T, L, H, W)}, got {tuple(dew.shape)}")
-        _dense_state(dew, "dew")
+        dense_state(dew, "dew", "postprocess", fp32=True)
     trig, th, tw = spec.trig_tables(lat_deg, lon_deg, output.device)
     if (th, tw) != (H, W):
         raise ValueError(f"postprocess: lat/lon of {th} x {tw} points for a {H} x {W} state")

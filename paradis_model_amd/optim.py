@@ -8,6 +8,7 @@ import torch
 
 from . import ops
 from ._lib import check, dptr, lib, require_hip, stream_ptr
+from ._tables import AddressTable, chunk_list
 
 
 class AdamW(torch.optim.Optimizer):
@@ -158,62 +159,41 @@ class AdamW(torch.optim.Optimizer):
     def snapshot_pointer_tables(self):
         """copies of the pinned address tables of the fused groups and of the Muon-family matrix groups
         (``harness.GraphedTrainStep``: a captured step re-reads them on every replay)"""
-        return {key: c["host"].clone() for key, c in self._pointer_caches()}
+        return {key: c["addr"].snapshot() for key, c in self._pointer_caches()}
 
     def restore_pointer_tables(self, tables) -> None:
         caches = dict(self._pointer_caches())
         for key, t in tables.items():
             c = caches.get(key)
-            if c is not None and c["host"].numel() == t.numel():
-                if c.get("pending") is not None:
-                    c["pending"].synchronize()
-                c["host"].copy_(t)
+            if c is not None:
+                c["addr"].restore(t)
 
     def _step_group_fused(self, gi, group, params, step, st, dev_state=None):
         """One launch for the group (``paradis_adamw_multi_d``).  Only the chunk list (a function of the
         parameter sizes) is cached; the four address rows (parameter, gradient, both moments) are
-        rewritten every step - ``load_state_dict``, ``p.data = ...`` or ``model.to()`` replace tensors
-        behind the same parameter ids - and reach the device through a pinned staging buffer without a
-        host synchronisation."""
+        rewritten every step (``_tables.AddressTable``)."""
         dev = params[0].device
         key = tuple((id(p), p.numel()) for p in params) + (str(dev),)
         cache = self.__dict__.setdefault("_fused_cache", {})
         c = cache.get(gi)
         if c is None or c["key"] != key:
             T = len(params)
-            chunk = lib.paradis_adamw_chunk()
-            ct, co = [], []
-            for t, p in enumerate(params):
-                for off in range(0, p.numel(), chunk):
-                    ct.append(t)
-                    co.append(off)
-            host = torch.empty(4 * T, dtype=torch.int64).pin_memory()
+            ct, co = chunk_list([p.numel() for p in params], lib.paradis_adamw_chunk())
             c = cache[gi] = dict(
-                key=key, T=T, host=host, ptrs=torch.empty(4 * T, dtype=torch.int64, device=dev),
+                key=key, T=T, addr=AddressTable(4, T, dev),
                 numel=torch.tensor([p.numel() for p in params], dtype=torch.int64, device=dev),
                 chunk_tensor=torch.tensor(ct, dtype=torch.int32, device=dev),
                 chunk_off=torch.tensor(co, dtype=torch.int64, device=dev), n_chunks=len(ct))
-        T, host = c["T"], c["host"]
-        capturing = torch.cuda.is_current_stream_capturing()
-        if c.get("pending") is not None and not capturing:     # the previous step's async copy out of `host` (long done)
-            c["pending"].synchronize()
+        T = c["T"]
         moments = [(self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in params]
         for m, v in moments:
             require_hip(m, v)
             if not (m.is_contiguous() and v.is_contiguous()):
                 raise RuntimeError("AdamW: non-contiguous optimizer state")
-        host.copy_(torch.tensor([p.data_ptr() for p in params] + [p.grad.data_ptr() for p in params]
-                                + [m.data_ptr() for m, _ in moments] + [v.data_ptr() for _, v in moments],
-                                dtype=torch.int64))
-        c["ptrs"].copy_(host, non_blocking=True)
-        if capturing:
-            c["pending"] = None      # (inside a capture the copy is a graph node; nothing to wait for on the host)
-        else:
-            ev = torch.cuda.Event()
-            ev.record()
-            c["pending"] = ev
+        c["addr"].write([p.data_ptr() for p in params] + [p.grad.data_ptr() for p in params]
+                        + [m.data_ptr() for m, _ in moments] + [v.data_ptr() for _, v in moments])
         b1, b2 = group["betas"]
-        check(lib.paradis_adamw_multi_d(dptr(c["ptrs"]), dptr(c["numel"]), dptr(c["chunk_tensor"]),
+        check(lib.paradis_adamw_multi_d(dptr(c["addr"].ptrs), dptr(c["numel"]), dptr(c["chunk_tensor"]),
                                       dptr(c["chunk_off"]), T, c["n_chunks"], group["lr"], b1, b2, group["eps"],
                                       group["weight_decay"], step, dptr(dev_state), st), "adamw_multi")
 
@@ -352,8 +332,8 @@ class Muon(AdamW):
     def _step_matrix_group(self, pl):
         """Same-shaped matrices are updated together (one ``paradis_muon_step`` per shape: the batched
         Newton-Schulz GEMMs fill the chip).  One device table of the w / g / momentum / variance
-        addresses serves all shapes; the gradient addresses are refreshed each step through a pinned
-        staging buffer (no host synchronisation).  Capturable: the learning rate is read from the group's device
+        addresses serves all shapes; all four rows are rewritten each step (``_tables.AddressTable``: state tensors
+        can be replaced by ``load_state_dict`` behind the same parameter ids).  Capturable: the learning rate is read from the group's device
         state (``paradis_muon_step_d``), and inside a graph capture the table copy is a graph node, as in
         ``_step_group_fused``."""
         gi, group, params = pl["gi"], pl["group"], pl["params"]
@@ -371,38 +351,23 @@ class Muon(AdamW):
                 shapes.append((rows, cols, full, len(order), len(ps)))
                 order.extend(ps)
             T = len(order)
-            host = torch.zeros(4 * T, dtype=torch.int64).pin_memory()
             ws_bytes = max(lib.paradis_muon_ws_bytes(n, rows, cols) for rows, cols, _, _, n in shapes)
-            c = cache[gi] = dict(key=key, order=order, shapes=shapes, T=T, host=host,
-                                 table=torch.empty(4 * T, dtype=torch.int64, device=dev),
+            c = cache[gi] = dict(key=key, order=order, shapes=shapes, T=T, addr=AddressTable(4, T, dev),
                                  ws=torch.empty(ws_bytes // 4 + 64, dtype=torch.float32, device=dev))
-        T, host = c["T"], c["host"]
-        capturing = torch.cuda.is_current_stream_capturing()
-        if c.get("pending") is not None and not capturing:     # the previous step's async copy out of `host` (long done)
-            c["pending"].synchronize()
+        T = c["T"]
         grads = []
         for p in c["order"]:
             g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
             grads.append(g)          # keep alive until the kernels are queued
-        # all four address rows are rewritten every step (state tensors can be replaced by
-        # load_state_dict behind the same parameter ids)
         mom = [self.state[p]["momentum"] for p in c["order"]]
         var = [self.state[p]["variance_neuron"] for p in c["order"]] if normuon else []
         require_hip(*mom, *var)
-        host.copy_(torch.tensor([p.data_ptr() for p in c["order"]] + [g.data_ptr() for g in grads]
-                                + [m.data_ptr() for m in mom]
-                                + ([v.data_ptr() for v in var] if normuon else [0] * T), dtype=torch.int64))
-        c["table"].copy_(host, non_blocking=True)
-        if capturing:
-            c["pending"] = None      # (inside a capture the copy is a graph node; nothing to wait for on the host)
+        if c["addr"].write([p.data_ptr() for p in c["order"]] + [g.data_ptr() for g in grads]
+                           + [m.data_ptr() for m in mom] + ([v.data_ptr() for v in var] if normuon else [0] * T)):
             c["captured_grads"] = grads      # every replay reads them at these addresses: they live as long as the table
-        else:
-            ev = torch.cuda.Event()
-            ev.record()
-            c["pending"] = ev
         st = stream_ptr()
         lr = group["lr"]
-        base = c["table"].data_ptr()
+        base = c["addr"].ptrs.data_ptr()
         split = 1 if ops.GEMM_SCHEME != ops.GEMM_EXACT else 0
         for rows, cols, full, off, n in c["shapes"]:
             if self.capturable:

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib, harness
 from ._lib import dptr, require_hip, stream_ptr
+from ._tables import dense_state, workspace
 from .feed import KIND_HUMIDITY, KIND_PRECIP, KIND_ZSCORE
 from .forecast import _GraphedStep
 
@@ -103,20 +104,6 @@ class ReportSpec:
 _WS: Dict[tuple, torch.Tensor] = {}
 
 
-def _workspace(device, nbytes: int) -> torch.Tensor:
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    ws = _WS.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        with torch.inference_mode(False):
-            ws = _WS[key] = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
-    return ws
-
-
-def _dense_state(t: torch.Tensor, what: str) -> None:
-    if t.stride(-1) != 1 or t.stride(-2) != t.shape[-1] or t.stride(-3) != t.shape[-1] * t.shape[-2]:
-        raise ValueError(f"score: {what} must hold dense [C, H, W] states")
-
-
 def row_size(C: int, R: int) -> int:
     return 1 + 2 * C + R
 
@@ -140,8 +127,8 @@ def score(pred: torch.Tensor, target: torch.Tensor, loss, reports: Optional[Repo
     R = reports.num_reports if reports is not None else 0
     if out_row.dim() != 1 or out_row.numel() != row_size(C, R) or out_row.stride(0) != 1:
         raise ValueError(f"score: out_row must be a dense vector of 1 + 2*{C} + {R} entries")
-    _dense_state(pred, "pred")
-    _dense_state(target, "target")
+    dense_state(pred, "pred", "score")
+    dense_state(target, "target", "score")
     wf = loss.feature_weights_buf.reshape(-1)
     lat = loss.lat_weights_buf.reshape(-1)
     require_hip(wf, lat)
@@ -157,7 +144,7 @@ def score(pred: torch.Tensor, target: torch.Tensor, loss, reports: Optional[Repo
     tabs = reports.device_tables(pred.device, C) if R else (None,) * 5
     chan_h = reports.chan.ctypes.data_as(ctypes.c_void_p) if R else None
     cls_h = reports.cls.ctypes.data_as(ctypes.c_void_p) if R else None
-    ws = _workspace(pred.device, int(_lib.lib.paradis_val_score_ws_bytes(B, C, H, W)))
+    ws = workspace(_WS, pred.device, int(_lib.lib.paradis_val_score_ws_bytes(B, C, H, W)))
     _lib.call("val_score", 8.0 * B * C * P, dptr(pred), bs(pred), dptr(target), bs(target), dptr(wf), dptr(wl),
               dptr(lat) if R else None, LOSS_KIND[loss.kind], float(loss.delta), chan_h, cls_h, R,
               *(dptr(t) for t in tabs), dptr(out_row), dptr(ws), B, C, H, W, stream_ptr())

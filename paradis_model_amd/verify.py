@@ -33,14 +33,10 @@ import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
+from ._tables import dense_state, workspace
 
 ACC_FIELDS = 8          # {n, sum se, sum e, sum ae, sum acc_b, n_acc, sum ff, sum tt}
 METRICS = ("rmse", "bias", "mae", "acc", "activity")
-
-
-def _dense_state(t: torch.Tensor, what: str) -> None:
-    if t.stride(-1) != 1 or t.stride(-2) != t.shape[-1] or t.stride(-3) != t.shape[-1] * t.shape[-2]:
-        raise ValueError(f"Scorecard.update: {what} must hold dense [C, H, W] states")
 
 
 def lat_weights_from(loss) -> torch.Tensor:
@@ -99,14 +95,6 @@ class Scorecard:
 
     lat_weights_from = staticmethod(lat_weights_from)
 
-    def _workspace(self, device, nbytes: int) -> torch.Tensor:
-        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() * 8 < nbytes:
-            with torch.inference_mode(False):
-                ws = self._ws[key] = torch.empty(max(1, (nbytes + 7) // 8), dtype=torch.float64, device=device)
-        return ws
-
     def _check(self, lead, forecast, truth, clim_index):
         """argument checks of ``update``; returns (B, C, H, W)"""
         if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < self.n_leads:
@@ -123,8 +111,8 @@ class Scorecard:
                              f"and {H} latitudes")
         if truth.shape != forecast.shape:
             raise ValueError(f"Scorecard.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
-        _dense_state(forecast, "forecast")
-        _dense_state(truth, "truth")
+        dense_state(forecast, "forecast", "Scorecard.update")
+        dense_state(truth, "truth", "Scorecard.update")
         if self.climatology is None:
             if clim_index is not None:
                 raise ValueError("Scorecard.update: clim_index given, but the scorecard has no climatology")
@@ -163,7 +151,7 @@ class Scorecard:
             return t.stride(0) if B > 1 else C * P
 
         with_clim = clim is not None
-        ws = self._workspace(forecast.device, int(_lib.lib.paradis_verify_ws_bytes(B, C, H, W, int(with_clim))))
+        ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_verify_ws_bytes(B, C, H, W, int(with_clim))))
         _lib.call("verify_update", (12.0 if with_clim else 8.0) * B * C * P, dptr(forecast), bs(forecast), dptr(truth),
                   bs(truth), dptr(clim), dptr(clim_index) if with_clim else None, clim.shape[0] if with_clim else 0,
                   dptr(self.lat_w), float(W) * self._wsum, dptr(self.acc[int(lead)]), dptr(ws), B, C, H, W,
