@@ -138,7 +138,7 @@ class Paradis(nn.Module):
 
     # ``Paradis.compile(mode=..., fullgraph=True, dynamic=False, backend="inductor")`` (reference
     # trainer.py:261-267) is ``nn.Module.compile``: the ops are registered with fake kernels and autograd
-    # formulas (paradis_model_amd/ops.py), so the whole forward traces into one graph.
+    # formulas (paradis_model_amd/ops/), so the whole forward traces into one graph.
 
     def upsample(self, x: torch.Tensor) -> torch.Tensor:
         """Longitude-periodic bilinear interpolation to (nlat, nlon), align_corners=True."""
