@@ -425,6 +425,29 @@ int paradis_forcings(const int64_t* times_us /* [B,T] */, const double* lat_deg,
 int paradis_normalize_features(float* data, const int* kind, const float* p0, const float* p1,
                                int64_t rows, int C, float eps_q, int inverse, void* stream);
 
+/* Batch assembly from a device-resident store (reference data/era5_dataset.py:337-423 with the store held in HBM): ONE
+ * launch writes the input and the target of B samples from store[T, F, H, W] (channels first, float32),
+ *   input [b, 0, k*Fin + j] = norm(store[t_in(b) + k, feature(j)]),   k < n_time_inputs, j < Fin
+ *   target[b, s, j]         = norm(store[t_in(b) + dt(s, j), feature(j)]),   s < S, j < Fout
+ * with t_in(b) = base + idx[b] * interval_steps.  planes: DEVICE table of n_time_inputs*Fin + S*Fout entries, one per
+ * output plane of a sample (the input's channels, then the target's, step-major): source feature, time offset from
+ * t_in, and the kind / p0 / p1 of paradis_normalize_features, whose arithmetic the launch shares bit for bit.
+ * idx: DEVICE int64 [B] (no host sync: the launch can be captured).  target == NULL: input only (the prediction-stage
+ * item; the table's first n_time_inputs*Fin entries are used).  A time row or a feature outside the store is clamped
+ * - nothing outside the store is ever read - and *flag (DEVICE int, owned by the caller, never cleared here) is set to
+ * 1.  Float4 accesses when H*W % 4 == 0 and the three bases are 16-byte aligned, scalar otherwise.  Arguments are
+ * checked before any HIP call; B == 0 does nothing.  paradis_assemble_batch_chunk(): values per workgroup. */
+typedef struct {
+  int32_t feature; /* row of the store's feature axis */
+  int32_t dt;      /* time rows after t_in */
+  int32_t kind;    /* 0 none, 1 z-score, 2 specific humidity, 3 precipitation */
+  float p0, p1;    /* mean, std | q_min, q_max */
+} paradis_plane_t;
+int paradis_assemble_batch_chunk(void);
+int paradis_assemble_batch(const float* store, int64_t T, int F, int H, int W, const int64_t* idx, int B, int64_t base,
+                           int64_t interval_steps, const paradis_plane_t* planes, int n_time_inputs, int Fin, int S,
+                           int Fout, float* input, float* target, float eps_q, int* flag, void* stream);
+
 /* ---- f5: forecast post-processing (reference trainer.py:772-778 = utils/postprocessing.py:190-215 de-normalisation
  * + utils/postprocessing.py:74-122,143-187 Cartesian -> spherical winds, and the dew-point depression of
  * utils/mhuaes.py:33-96 that utils/file_output.py:165-173 derives - all on the CPU there).  One pass: reads the

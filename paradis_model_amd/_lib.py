@@ -56,6 +56,8 @@ SIGNATURES = {
     "paradis_forcings_ws_bytes": (ctypes.c_size_t, [I, I]),
     "paradis_forcings": (I, [P, P, P, I, I, I, I, I, I, P, I, ctypes.c_double, ctypes.c_double, P, P, P]),
     "paradis_normalize_features": (I, [P, P, P, P, L, I, ctypes.c_float, I, P]),
+    "paradis_assemble_batch_chunk": (I, []),
+    "paradis_assemble_batch": (I, [P, L, I, I, I, P, I, L, L, P, I, I, I, I, P, P, F, P, P]),
     "paradis_global_bias_m8_fwd": (I, [P, P, P, P, I, I, I, I, P]),
     "paradis_global_bias_m8_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P]),
     "paradis_global_bias_proj_bwd": (I, [P, P, P, P, P, I, I, L, P]),

@@ -152,17 +152,10 @@ forcings_kernel(const double* __restrict__ lat_deg, const double* __restrict__ l
   }
 }
 
-// channels-last feature (de)normalisation, in place: data[i, c], kind[c] in {0 none, 1 z-score (p0 mean,
-// p1 std), 2 humidity (p0 q_min, p1 q_max), 3 precipitation}
-__global__ void __launch_bounds__(256)
-normalize_kernel(float* __restrict__ data, const int* __restrict__ kind, const float* __restrict__ p0,
-                 const float* __restrict__ p1, int64_t n, int C, float eps_q, int inverse) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int c = (int)(i % C);
-  const int k = kind[c];
-  if (k == 0) return;
-  const float x = data[i], a = p0[c], b = p1[c];
+// one value through one feature normalisation (reference utils/normalization.py:6-80): k in {0 none, 1 z-score (a mean,
+// b std), 2 humidity (a q_min, b q_max), 3 precipitation}.  The ONE expression of the unit: normalize_kernel and
+// assemble_batch_kernel both call it, so a plane assembled by the second equals the first applied to a gathered copy.
+__device__ __forceinline__ float normalize_value(float x, int k, float a, float b, float eps_q, int inverse) {
   float r = x;
   if (k == 1) {
     r = inverse ? x * b + a : (x - a) / b;
@@ -177,7 +170,76 @@ normalize_kernel(float* __restrict__ data, const int* __restrict__ kind, const f
   } else if (k == 3) {
     r = inverse ? fmaxf(expf(x - 10.0f) - 1e-6f, 0.f) : logf(x + 1e-6f) + 10.0f;
   }
-  data[i] = r;
+  return r;
+}
+
+// channels-last feature (de)normalisation, in place: data[i, c], kind[c] in {0 none, 1 z-score (p0 mean,
+// p1 std), 2 humidity (p0 q_min, p1 q_max), 3 precipitation}
+__global__ void __launch_bounds__(256)
+normalize_kernel(float* __restrict__ data, const int* __restrict__ kind, const float* __restrict__ p0,
+                 const float* __restrict__ p1, int64_t n, int C, float eps_q, int inverse) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  const int k = kind[c];
+  if (k == 0) return;
+  data[i] = normalize_value(data[i], k, p0[c], p1[c], eps_q, inverse);
+}
+
+// Batch assembly from a device-resident channels-first store [T, F, P] (P = H*W): one workgroup copies one chunk of
+// AB_CHUNK = AB_THREADS * 4 * AB_UNROLL values of ONE output plane through that plane's normalisation, so the table
+// entry, the sample's time row and both plane addresses are wave-uniform (scalar loads, no divergence in the kind
+// switch).  Planes [0, n_in) of a sample are the input's channels, [n_in, n_in + n_out) the target's (step-major).
+// 8 B of HBM traffic per value.  Rows and features outside the store are CLAMPED (never read outside) and reported
+// through *flag; a negative or enormous idx[b] is limited first so that base + idx * interval cannot wrap.
+constexpr int AB_THREADS = 256, AB_UNROLL = 2, AB_CHUNK = AB_THREADS * 4 * AB_UNROLL;
+
+__global__ void __launch_bounds__(AB_THREADS)
+assemble_batch_kernel(const float* __restrict__ store, int64_t T, int F, int64_t P, const int64_t* __restrict__ idx,
+                      int64_t base, int64_t interval, const paradis_plane_t* __restrict__ planes, int n_in, int n_out,
+                      int chunks, float* __restrict__ input, float* __restrict__ target, float eps_q,
+                      int* __restrict__ flag, int vec) {
+  const uint32_t blk = blockIdx.x, r = blk / (uint32_t)chunks;     // the grid is below 2^31: 32-bit divisions
+  const int chunk = (int)(blk - r * (uint32_t)chunks);
+  const uint32_t np = (uint32_t)(n_in + n_out);
+  const int64_t b = r / np;
+  const int plane = (int)(r - (uint32_t)b * np);
+  const paradis_plane_t e = planes[plane];
+  constexpr int64_t IDX_LIMIT = 1ll << 40;
+  const int64_t i_raw = idx[b];
+  const int64_t i_ok = i_raw < -IDX_LIMIT ? -IDX_LIMIT : (i_raw > IDX_LIMIT ? IDX_LIMIT : i_raw);
+  const int64_t row_raw = base + i_ok * interval + e.dt;
+  const int64_t row = row_raw < 0 ? 0 : (row_raw >= T ? T - 1 : row_raw);
+  const int f = e.feature < 0 ? 0 : (e.feature >= F ? F - 1 : e.feature);
+  if ((row != row_raw || f != e.feature) && threadIdx.x == 0) *flag = 1;
+  const float* __restrict__ src = store + (row * F + f) * P;
+  float* __restrict__ dst = plane < n_in ? input + (b * n_in + plane) * P : target + (b * n_out + (plane - n_in)) * P;
+  const int64_t lo = (int64_t)chunk * AB_CHUNK;
+  const int64_t hi = lo + AB_CHUNK < P ? lo + AB_CHUNK : P;
+  const int k = e.kind;
+  const float a = e.p0, c = e.p1;
+  if (vec) {    // P % 4 == 0 and 16-byte aligned bases: lo, hi and every plane base are multiples of four floats
+    float4 q[AB_UNROLL];
+#pragma unroll
+    for (int u = 0; u < AB_UNROLL; ++u) {
+      const int64_t i = lo + (int64_t)(u * AB_THREADS + threadIdx.x) * 4;
+      if (i < hi) q[u] = *reinterpret_cast<const float4*>(src + i);
+    }
+#pragma unroll
+    for (int u = 0; u < AB_UNROLL; ++u) {
+      const int64_t i = lo + (int64_t)(u * AB_THREADS + threadIdx.x) * 4;
+      if (i < hi) {
+        float4 o;
+        o.x = normalize_value(q[u].x, k, a, c, eps_q, 0);
+        o.y = normalize_value(q[u].y, k, a, c, eps_q, 0);
+        o.z = normalize_value(q[u].z, k, a, c, eps_q, 0);
+        o.w = normalize_value(q[u].w, k, a, c, eps_q, 0);
+        *reinterpret_cast<float4*>(dst + i) = o;
+      }
+    }
+  } else {
+    for (int64_t i = lo + threadIdx.x; i < hi; i += AB_THREADS) dst[i] = normalize_value(src[i], k, a, c, eps_q, 0);
+  }
 }
 
 }  // namespace
@@ -228,5 +290,37 @@ extern "C" int paradis_normalize_features(float* data, const int* kind, const fl
   hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, data,
                      kind, p0, p1, n, C, eps_q, inverse);
   PD_CHECK_LAUNCH("normalize_features");
+  return 0;
+}
+
+extern "C" int paradis_assemble_batch_chunk(void) { return AB_CHUNK; }
+
+extern "C" int paradis_assemble_batch(const float* store, int64_t T, int F, int H, int W, const int64_t* idx, int B,
+                                      int64_t base, int64_t interval_steps, const paradis_plane_t* planes,
+                                      int n_time_inputs, int Fin, int S, int Fout, float* input, float* target,
+                                      float eps_q, int* flag, void* stream) {
+  PD_REQUIRE(T >= 1 && F >= 1 && H >= 1 && W >= 1 && B >= 0, "assemble_batch: bad shape T=%lld F=%d H=%d W=%d B=%d",
+             (long long)T, F, H, W, B);
+  PD_REQUIRE(n_time_inputs >= 1, "assemble_batch: n_time_inputs=%d must be >= 1", n_time_inputs);
+  PD_REQUIRE(S >= 0, "assemble_batch: forecast steps S=%d must be >= 0", S);
+  PD_REQUIRE(Fin >= 1 && Fout >= 0, "assemble_batch: bad feature counts Fin=%d Fout=%d", Fin, Fout);
+  PD_REQUIRE(interval_steps >= 1, "assemble_batch: interval_steps=%lld must be >= 1", (long long)interval_steps);
+  PD_REQUIRE((int64_t)n_time_inputs * Fin < (1 << 24) && (int64_t)S * Fout < (1 << 24),
+             "assemble_batch: too many planes per sample");
+  PD_REQUIRE(planes != nullptr, "assemble_batch: plane table required");
+  if (B == 0) return 0;
+  PD_REQUIRE(store != nullptr && idx != nullptr && input != nullptr && flag != nullptr,
+             "assemble_batch: store, idx, input and flag pointers required");
+  const int n_in = n_time_inputs * Fin;
+  const int n_out = target != nullptr ? S * Fout : 0;     // no target: the prediction-stage item
+  const int64_t P = (int64_t)H * W;
+  const int64_t chunks = ceil_div64(P, AB_CHUNK);
+  PD_REQUIRE(chunks < (1ll << 31), "assemble_batch: grid too large");
+  const int64_t blocks = (int64_t)B * (n_in + n_out) * chunks;
+  PD_REQUIRE(blocks < (1ll << 31), "assemble_batch: too large (%lld workgroups)", (long long)blocks);
+  const int vec = P % 4 == 0 && aligned16(store) && aligned16(input) && (target == nullptr || aligned16(target));
+  hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)blocks), dim3(AB_THREADS), 0, (hipStream_t)stream, store, T,
+                     F, P, idx, base, interval_steps, planes, n_in, n_out, (int)chunks, input, target, eps_q, flag, vec);
+  PD_CHECK_LAUNCH("assemble_batch");
   return 0;
 }

@@ -318,7 +318,16 @@ class GraphedTrainStep:
     captured with the step.  With ``accumulate_grad_batches`` = N > 1 the unit of capture is the WINDOW: ``example_batch``
     is a sequence of N batches, ``__call__(batches)`` copies N batches into the static buffers, makes ONE replay and returns
     the static ``[N]`` losses; ``eager_step(batches)`` runs ``TrainStep.window``.  A DDP-wrapped model with N > 1 is not
-    supported under capture yet (eager DDP with N > 1 works as in the reference: one all-reduce round per backward)."""
+    supported under capture yet (eager DDP with N > 1 works as in the reference: one all-reduce round per backward).
+
+    Feeding the static buffers in place: ``__call__`` skips the copy of a tensor that already IS its static buffer, so a
+    ``dataset.DeviceDataset`` can assemble every batch straight into them -
+
+        for idx in index_batches:                       # device int64 vectors, e.g. slices of one epoch permutation
+            ds.batch(idx, out=g.static_batch)           # one assembly launch + the forcings launch, no host sync
+            loss = g(g.static_batch)                    # no copies: one graph replay
+
+    (``tests/test_hip_dataset.py::test_graphed_train_step_fed_in_place``)."""
 
     DDP_WARMUP = 11
 
