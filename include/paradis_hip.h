@@ -559,6 +559,54 @@ int paradis_verify_update(const float* fc, int64_t fc_bs, const float* truth, in
                           const int* clim_index, int K, const float* lat_w, double Z, double* acc, void* ws, int B,
                           int C, int H, int W, void* stream);
 
+/* ---- Store preparation (reference scripts/preprocess_dataset.py: compute_statistics :409-479,
+ * compute_tendency_statistics :482-590, compute_cartesian_wind :42-105), csrc/prepare.hip.
+ *
+ * paradis_store_stats: one pass over a slab x [T, F, H, W] fp32 (dense) that merges into a running accumulator, per
+ * feature and over every non-NaN value (skipna=True: NaN is skipped, nothing else),
+ *   {n, sum (x - pivot), sum (x - pivot)^2, min, max}                               into set field_set (>= 0), and / or
+ *   the same five of d = x[t] - x[t - stride] (float32 difference, pivot 0, NaN d skipped) into set tend_set (>= 0);
+ * -1 leaves a set out.  A pair is counted with its later row, t = 0 .. T - 1; rows t - stride < 0 are the LAST rows of
+ * prev [n_prev, F, H, W] (the rows seen before x; NULL / 0: none), pairs reaching further back are not counted.
+ *   acc: DEVICE double [F][n_sets + 1][5].  Sets 0 .. n_sets - 1 hold the five quantities; the caller initialises them
+ *   to {0, 0, 0, +inf, -inf}.  Row n_sets of a feature is {pivot, pivot_is_set, 0, 0, 0}, initialised to zeros: the
+ *   first call with a field set stores the first non-NaN cell (index order) of plane f of row 0 there, 0 if it has
+ *   none, and every later call uses that value.  Read and written by ordinary accesses (calls on one stream are ordered).
+ * Everything after the fp32 load / difference is double; sums in a fixed order (csrc/stream_common.h), no atomics:
+ * bit-identical run to run for a given partition into slabs.  Three launches whatever T and F are; the workgroup
+ * count stays near 4096 + F * ceil(H*W / paradis_store_stats_piece()).
+ * ws: paradis_store_stats_ws_bytes(T, F, H, W) bytes, 8-byte aligned.  T == 0 does nothing.  rc 1 before any HIP call
+ * for: F / H / W < 1, a set outside [-1, n_sets), both sets -1 or equal, stride < 1 with a tendency, n_prev > 0 without
+ * prev, a NULL x / acc / ws, a grid above the launch limit.
+ * H*W % 4 == 0 with 16-byte aligned x and prev takes 16-byte loads, anything else scalar loads: the same bits.
+ * Algorithmic HBM bytes: 4*T*F*H*W for the field alone or with the tendency of stride 1 (the row just read stays in
+ * registers), 8*T*F*H*W with a longer stride or for a tendency alone.
+ *
+ * paradis_cartesian_winds: dst[t, row.dst_x / y / z] = Cartesian wind of src[t, row.src_u / v / w / t] for every table
+ * row and t < T in one launch; src [T, Fs, H, W], dst [T, Fd, H, W] fp32 dense, possibly the same tensor provided no
+ * row's destination is another row's source.  src_w = src_t = -1: a surface row (dr/dt = 0).  With k = (float32)(omega *
+ * 287.05 * T) / (level_hpa * 100 * 9.80616):
+ *   x = -u sin(lon) - v sin(lat) cos(lon) - k cos(lat) cos(lon)
+ *   y =  u cos(lon) - v sin(lat) sin(lon) - k cos(lat) sin(lon)
+ *   z =  v cos(lat) - k sin(lat)
+ * in double from the fp32 fields and trig = double [sin(lat)[H], cos(lat)[H], sin(lon)[W], cos(lon)[W]] (DEVICE, built
+ * on the host), rounded to fp32 once: what numpy gives the reference for float32 fields and float64 grids.  rows: DEVICE
+ * table; rows_host: the same table in host memory, checked (columns inside [0, Fs) / [0, Fd), level > 0) before any
+ * HIP call.  W % 4 == 0 with 16-byte aligned bases takes 16-byte accesses.  T == 0 or n_rows == 0 does nothing.
+ * Algorithmic HBM bytes per cell: 28 for a level row, 20 for a surface row. */
+typedef struct {
+  int32_t src_u, src_v, src_w, src_t; /* columns of src: u, v, omega (Pa/s), temperature; src_w = src_t = -1: surface */
+  int32_t dst_x, dst_y, dst_z;        /* columns of dst */
+  float level_hpa;                    /* pressure level in hPa (unused for a surface row) */
+} paradis_wind_row_t;
+int paradis_store_stats_piece(void);
+size_t paradis_store_stats_ws_bytes(int T, int F, int H, int W);
+int paradis_store_stats(const float* x, int T, const float* prev, int n_prev, int F, int H, int W, int field_set,
+                        int tend_set, int stride, double* acc, int n_sets, void* ws, void* stream);
+int paradis_cartesian_winds(const float* src, int Fs, float* dst, int Fd, const paradis_wind_row_t* rows,
+                            const paradis_wind_row_t* rows_host, int n_rows, const double* trig, int T, int H, int W,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,10 @@ SIGNATURES = {
     "paradis_verify_piece": (I, []),
     "paradis_verify_ws_bytes": (S, [I, I, I, I, I]),
     "paradis_verify_update": (I, [P, L, P, L, P, P, I, P, D, P, P, I, I, I, I, P]),
+    "paradis_store_stats_piece": (I, []),
+    "paradis_store_stats_ws_bytes": (S, [I, I, I, I]),
+    "paradis_store_stats": (I, [P, I, P, I, I, I, I, I, I, I, P, I, P, P]),
+    "paradis_cartesian_winds": (I, [P, I, P, I, P, P, I, P, I, I, I, P]),
 }
 
 _missing = []

@@ -1,11 +1,12 @@
 """Host side of the table-driven launches (``csrc/stream_common.h``): the chunk list of a tensor list, the address
 table that reaches the device through a pinned staging row, the per-stream workspace cache and the dense-state check
-of the plane kernels.  The pinned-row protocol lives here once: ``optim.AdamW``, ``optim.Muon``, ``clip.ClipPlan`` and
+of the plane kernels, and the trigonometric tables of the wind kernels.  The pinned-row protocol lives here once: ``optim.AdamW``, ``optim.Muon``, ``clip.ClipPlan`` and
 ``diagnostics.StatsPlan`` all go through ``AddressTable``."""
 from __future__ import annotations
 
 from typing import Dict, List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 
@@ -86,3 +87,22 @@ def dense_state(t: torch.Tensor, what: str, who: str, fp32: bool = False) -> Non
             raise ValueError(f"{who}: {what} must be float32 with dense [C, H, W] states")
     elif not dense:
         raise ValueError(f"{who}: {what} must hold dense [C, H, W] states")
+
+
+def trig_tables(cache: dict, lat_deg, lon_deg, device):
+    """(double [sin(lat)[H], cos(lat)[H], sin(lon)[W], cos(lon)[W]] on ``device``, H, W) out of the owner's ``cache``:
+    built once per grid on the host with numpy from the 1-D degree arrays (float32 arrays are widened first: float64
+    trigonometry of the stored values).  The tables of ``csrc/post.hip`` and ``csrc/prepare.hip``."""
+    if isinstance(lat_deg, torch.Tensor):
+        lat_deg = lat_deg.detach().cpu().numpy()
+    if isinstance(lon_deg, torch.Tensor):
+        lon_deg = lon_deg.detach().cpu().numpy()
+    lat = np.ascontiguousarray(np.asarray(lat_deg, np.float64).reshape(-1))
+    lon = np.ascontiguousarray(np.asarray(lon_deg, np.float64).reshape(-1))
+    key = (str(device), lat.tobytes(), lon.tobytes())
+    if key not in cache:
+        la, lo = np.deg2rad(lat), np.deg2rad(lon)
+        tab = np.concatenate([np.sin(la), np.cos(la), np.sin(lo), np.cos(lo)])
+        with torch.inference_mode(False):
+            cache[key] = (torch.from_numpy(tab).to(device), lat.size, lon.size)
+    return cache[key]

@@ -43,11 +43,13 @@ class DeviceStore:
     data: [T, F, H, W] float32 (numpy array, memmap or tensor), the on-disk layout ``time, features, latitude,
     longitude``; uploaded in time slabs, so a memmap never needs a second full host copy.  times: [T] datetime64 or int64
     microseconds, ascending.  features: the F names.  stats: dict of [F] arrays ``mean / std / min / max`` (the
-    reference's ``stats`` store).  lat_deg [H] ascending, lon_deg [W].  constants: the [H, W, Cc] tensor the reference's
-    dataset precomputes (``:193-251``).  toa_mean / toa_std: ``toa_radiation_mean / _std`` of the stats store."""
+    reference's ``stats`` store), or None: computed from the uploaded data (``prepare.store_statistics``).  lat_deg [H]
+    ascending, lon_deg [W].  constants: the [H, W, Cc] tensor the reference's dataset precomputes (``:193-251``).
+    toa_mean / toa_std: ``toa_radiation_mean / _std`` of the stats store, or None: computed from ``times`` and the grid
+    (``prepare.toa_radiation_stats``).  Computing either needs the HIP device."""
 
-    def __init__(self, data, times, features: Sequence[str], stats, lat_deg, lon_deg, constants, toa_mean: float,
-                 toa_std: float, device="cuda"):
+    def __init__(self, data, times, features: Sequence[str], stats, lat_deg, lon_deg, constants, toa_mean=None,
+                 toa_std=None, device="cuda"):
         if len(data.shape) != 4:
             raise ValueError(f"DeviceStore: data must be [T, F, H, W], got {tuple(data.shape)}")
         T, F, H, W = (int(v) for v in data.shape)
@@ -71,8 +73,11 @@ class DeviceStore:
         if H > 1 and not bool((lat[1:] > lat[:-1]).all()):
             # the reference sorts (era5_dataset.py:77-78); flipping 48 GB silently is not this class's business
             raise ValueError("DeviceStore: latitude must be ascending (sort the store's latitude axis first)")
+        if torch.device(device).type == "cpu" and (stats is None or toa_mean is None or toa_std is None):
+            raise ValueError("DeviceStore: statistics need the HIP device (stats=None / toa_mean=None / toa_std=None "
+                             "compute them there; this package has no CPU fallback)")
         self.stats = {}
-        for key in ("mean", "std", "min", "max"):
+        for key in ("mean", "std", "min", "max") if stats is not None else ():
             v = np.asarray(stats[key], dtype=np.float32).reshape(-1)      # float32 as era5_dataset.py:505-513
             if v.size != F:
                 raise ValueError(f"DeviceStore: stats['{key}'] has {v.size} entries for {F} features")
@@ -82,6 +87,11 @@ class DeviceStore:
         self.shape = (T, F, H, W)
         self.lat, self.lon = lat.cpu(), lon.cpu()
         self.lat_dev, self.lon_dev = lat.to(self.device), lon.to(self.device)
+        if toa_mean is None or toa_std is None:
+            from .prepare import toa_radiation_stats
+            mean, std = toa_radiation_stats(self.times_us, lat, lon, device=self.device)
+            toa_mean = mean if toa_mean is None else toa_mean
+            toa_std = std if toa_std is None else toa_std
         self.toa_mean, self.toa_std = float(toa_mean), float(toa_std)
         const = constants if isinstance(constants, torch.Tensor) else torch.as_tensor(np.asarray(constants))
         if const.dim() != 3 or tuple(const.shape[:2]) != (H, W):
@@ -95,6 +105,10 @@ class DeviceStore:
             if not isinstance(slab, torch.Tensor):
                 slab = torch.from_numpy(np.ascontiguousarray(slab))
             self.data[a:a + rows].copy_(slab)
+        if stats is None:
+            from .prepare import store_statistics
+            res = store_statistics(self.data)
+            self.stats = {key: res[key] for key in ("mean", "std", "min", "max")}
 
     def row_of(self, when_us: int, side: str = "left") -> int:
         """first store row at or after (``left``) / after (``right``) the given time"""

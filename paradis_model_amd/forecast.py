@@ -24,7 +24,7 @@ import torch
 
 from . import _lib, harness
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import dense_state
+from ._tables import dense_state, trig_tables
 from .feed import KIND_HUMIDITY, KIND_PRECIP, KIND_ZSCORE
 
 UNIT_SINGLE, UNIT_LEVEL, UNIT_SURFACE = 0, 1, 2
@@ -141,22 +141,9 @@ class PostSpec:
                     np.asarray(self.pressure_levels or [0.0], np.float64)))
         return self._dev[key]
 
-    def trig_tables(self, lat_deg, lon_deg, device) -> torch.Tensor:
-        """double [sin(lat)[H], cos(lat)[H], sin(lon)[W], cos(lon)[W]] on ``device``, built once per grid on the host with
-        numpy from the 1-D degree arrays (float32 arrays are widened first: float64 trigonometry of the stored values)."""
-        if isinstance(lat_deg, torch.Tensor):
-            lat_deg = lat_deg.detach().cpu().numpy()
-        if isinstance(lon_deg, torch.Tensor):
-            lon_deg = lon_deg.detach().cpu().numpy()
-        lat = np.ascontiguousarray(np.asarray(lat_deg, np.float64).reshape(-1))
-        lon = np.ascontiguousarray(np.asarray(lon_deg, np.float64).reshape(-1))
-        key = (str(device), lat.tobytes(), lon.tobytes())
-        if key not in self._trig:
-            la, lo = np.deg2rad(lat), np.deg2rad(lon)
-            tab = np.concatenate([np.sin(la), np.cos(la), np.sin(lo), np.cos(lo)])
-            with torch.inference_mode(False):
-                self._trig[key] = (torch.from_numpy(tab).to(device), lat.size, lon.size)
-        return self._trig[key]
+    def trig_tables(self, lat_deg, lon_deg, device):
+        """the double sin / cos tables of the grid on ``device``, built once (``_tables.trig_tables``)"""
+        return trig_tables(self._trig, lat_deg, lon_deg, device)
 
 
 def postprocess(output: torch.Tensor, spec: PostSpec, lat_deg, lon_deg, chunk: torch.Tensor, slot: int,
