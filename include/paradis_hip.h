@@ -467,6 +467,35 @@ int paradis_forecast_post(const float* output, int64_t out_bs, float* chunk, int
                           const float* p1, float eps_q, const int* units, int n_units, const double* plev,
                           int n_levels, const double* trig, int B, int C, int H, int W, void* stream);
 
+/* ---- f5, the writer's layout (ABI 10, additive): a flushed chunk [B, n, C, H, W] (batch / time strides chunk_bs /
+ * chunk_ts in elements, dense [C, H, W] states: a trailing partial chunk is a dense view of a larger buffer) and its
+ * dew-point chunk [B, n, L, H, W] (dew_bs / dew_ts; NULL: none) regrouped into the named variables the reference's
+ * writer builds (utils/file_output.py:66-175) and passed through BitRound(keepbits) (utils/file_output.py:18-24), in
+ * ONE launch on `stream`: no host synchronisation, no memset or copy nodes; neither source is written.
+ *   out: one buffer of out_elems floats.  Variable v owns the contiguous block [B, n_td, L_v, H, W]; the blocks follow
+ *   one another in table order.  The launch writes time slots [td_off, td_off + n) of every block and nothing else.
+ *   planes: DEVICE table, one row per output plane of a (sample, time slot); planes_host: the same rows in host memory,
+ *   checked against C, L and out_elems before any HIP call.  A row's plane lands at element
+ *     (first * B * n_td + (b * n_td + td_off + t) * levels + level) * H * W.
+ *   keepbits 1 .. 23 on the float32 bit pattern, in 32-bit unsigned arithmetic, for any input (NaN, infinities):
+ *     m = 23 - keepbits;  bits += ((bits >> m) & 1) + ((1 << (m - 1)) - 1);  bits &= 0xFFFFFFFF << m
+ *   (numcodecs' published BitRound.encode restated; not pinned against the package).  keepbits 23, or 0 (the filter
+ *   off), copies the bits unchanged.
+ * rc 1 before any HIP call for: keepbits outside 0 .. 23, td_off + n > n_td, strides shorter than a state (or than the
+ * n states of a sample), a NULL table, a row outside the sources or the buffer.  B == 0 does nothing.
+ * 16-byte accesses when H*W % 4 == 0 and every base and stride keeps 16-byte alignment, scalar ones otherwise: the
+ * same bits either way.  Algorithmic HBM bytes: 8 * B * n * n_planes * H * W. */
+typedef struct {
+  int32_t src;    /* >= 0: channel of the chunk; < 0: level (-1 - src) of the dew-point chunk */
+  int32_t first;  /* planes per (sample, time slot) of the variables in front of this plane's variable */
+  int32_t levels; /* L_v: the levels of this plane's variable (1 for a surface variable) */
+  int32_t level;  /* this plane's level within its variable */
+} paradis_encode_plane_t;
+int paradis_forecast_encode(const float* chunk, int64_t chunk_bs, int64_t chunk_ts, const float* dew, int64_t dew_bs,
+                            int64_t dew_ts, const paradis_encode_plane_t* planes,
+                            const paradis_encode_plane_t* planes_host, int n_planes, float* out, int64_t out_elems,
+                            int B, int n, int C, int L, int H, int W, int n_td, int td_off, int keepbits, void* stream);
+
 /* ---- validation scores (reference trainer.py:652-708, _get_report_rmse trainer.py:291-315, per-channel loss
  * utils/loss.py:105-127).  One pass over pred and target [B, C, H, W] fp32 (batch strides pred_bs / target_bs in
  * elements, dense states; neither is written) and a finishing kernel that combines the per-workgroup partials in

@@ -113,6 +113,7 @@ SIGNATURES = {
     "paradis_amse_ws_bytes": (S, [I, I]),
     "paradis_amse_loss": (I, [P, P, P, P, P, P, P, I, I, I, P]),
     "paradis_forecast_post": (I, [P, L, P, L, L, P, L, L, P, P, P, F, P, I, P, I, P, I, I, I, I, P]),
+    "paradis_forecast_encode": (I, [P, L, L, P, L, L, P, P, I, P, L, I, I, I, I, I, I, I, I, I, P]),
     "paradis_val_score_ws_bytes": (S, [I, I, I, I]),
     "paradis_val_score": (I, [P, L, P, L, P, P, P, I, F, P, P, I, P, P, P, P, P, P, P, I, I, I, I, P]),
     "paradis_param_stats_chunk": (I, []),

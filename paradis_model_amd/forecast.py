@@ -267,7 +267,19 @@ class Forecaster:
     front of the event the side-stream copy waits for).  ``truth_normalized=True``: the truth is in model space (a
     validation batch's ``true_data``) and goes through the same ``postprocess`` into a scratch state first.  Without a
     scorecard ``run`` issues exactly the launches it issued before; a scorecard without ``truth``, or a truth of another
-    ``n_stored``, is refused before the rollout starts."""
+    ``n_stored``, is refused before the rollout starts.
+
+    ``run(..., encoder=<encode.EncodeSpec>, init=<(state [B, 1, C, H, W], dew [B, 1, L, H, W] or None) or None>)``: a
+    flushed chunk is regrouped into the writer's named variables and BitRounded on the device (``encode.encode_chunk``,
+    one launch on the main stream in front of the event the side-stream copy waits for) into one of two encoded device
+    buffers; the side stream copies that buffer - not the plain chunk - into one of two pinned buffers of the same layout
+    and ``on_chunk(variables=<dict name -> numpy view [B, n_td, (L,) H, W]>, start_idx=<int>, pred_slice=<slice>)`` is
+    called with the hand-over timing described above.  With ``init`` (``encode.initial_state``) the first chunk carries
+    that state in slot 0 (``n_td = n + 1``, ``pred_slice = slice(0, 1 + n)``, as the reference's writer); without it,
+    and for every later chunk, ``n_td = n`` and ``pred_slice = slice(1 + start_idx, 1 + start_idx + n)``.  A scorecard
+    keeps scoring the un-encoded state.  Refused before the rollout starts: an encoder whose names are not
+    ``PostSpec.names``, one with ``dewpoint=True`` on a forecaster without the dew point, an ``init`` of another shape.
+    Without ``encoder`` ``run`` issues exactly the launches it issued before."""
 
     def __init__(self, model, spec: PostSpec, lat_deg, lon_deg, *, num_common: int = 83, n_inputs: int = 2,
                  output_frequency: int = 1, write_every_n: Optional[int] = None, graph: bool = True,
@@ -282,20 +294,26 @@ class Forecaster:
         self._steps = {}       # (B, H, W) -> _GraphedStep
         self._bufs = {}        # chunk shape -> device chunks, pinned buffers, events
         self._truth = {}       # (B, C, H, W, device) -> [B, 1, C, H, W]: a model-space truth state in physical units
+        self._enc = {}         # chunk shape -> two encoded device buffers, two pinned buffers of the same layout
 
-    def _buffers(self, B, n, C, L, H, W, device):
+    def _buffers(self, B, n, C, L, H, W, device, pinned=True):
+        """device chunks, pinned buffers, events; ``pinned=False`` (the encoded hand-over, which has pinned buffers of its
+        own layout) leaves the plain pinned buffers unallocated until a run needs them"""
         key = (B, n, C, L, H, W, str(device), self.dewpoint)
-        if key not in self._bufs:
-            with torch.inference_mode(False):
+        with torch.inference_mode(False):
+            if key not in self._bufs:
                 dev = [torch.empty(B, n, C, H, W, device=device) for _ in range(2)]
-                host = [torch.empty(B, n, C, H, W, pin_memory=True) for _ in range(2)]
-                ddev = dhost = [None, None]
+                ddev = [None, None]
                 if self.dewpoint:
                     ddev = [torch.empty(B, n, L, H, W, device=device) for _ in range(2)]
-                    dhost = [torch.empty(B, n, L, H, W, pin_memory=True) for _ in range(2)]
-                self._bufs[key] = (dev, host, ddev, dhost, [torch.cuda.Event() for _ in range(2)],
+                self._bufs[key] = (dev, [None, None], ddev, [None, None], [torch.cuda.Event() for _ in range(2)],
                                    [torch.cuda.Event() for _ in range(2)], torch.cuda.Stream(device=device),
                                    [False, False])
+            host, dhost = self._bufs[key][1], self._bufs[key][3]
+            if pinned and host[0] is None:
+                host[:] = [torch.empty(B, n, C, H, W, pin_memory=True) for _ in range(2)]
+                if self.dewpoint:
+                    dhost[:] = [torch.empty(B, n, L, H, W, pin_memory=True) for _ in range(2)]
         return self._bufs[key]
 
     def _check_verification(self, scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W):
@@ -324,10 +342,43 @@ class Forecaster:
                 self._truth[key] = torch.empty(B, 1, C, H, W, device=truth.device)
         return self._truth[key]
 
+    def _check_encoder(self, encoder, init, B, C, L, H, W):
+        """the refusals of ``run(encoder=...)``, before the rollout starts; returns ``init`` as ``(state, dew or None)``"""
+        if encoder is None:
+            if init is not None:
+                raise ValueError("Forecaster.run: init goes with an encoder")
+            return None
+        if list(encoder.names) != list(self.spec.names):
+            raise ValueError("Forecaster.run: the encoder's names are not the chunk's channel names (PostSpec.names)")
+        if encoder.dewpoint and not self.dewpoint:
+            raise ValueError("Forecaster.run: the encoder writes dewpoint_depression, the forecaster has no dew point")
+        if encoder.num_levels != L:
+            raise ValueError(f"Forecaster.run: the encoder has {encoder.num_levels} levels, the chunk {L}")
+        if init is None:
+            return None
+        state, dew = init
+        if not encoder.dewpoint:
+            dew = None
+        elif dew is None:
+            raise ValueError("Forecaster.run: the encoder writes dewpoint_depression, init has no dew point")
+        require_hip(state, dew)
+        if tuple(state.shape) != (B, 1, C, H, W) or (dew is not None and tuple(dew.shape) != (B, 1, L, H, W)):
+            raise ValueError(f"Forecaster.run: init must be ({(B, 1, C, H, W)}, {(B, 1, L, H, W)} or None)")
+        return state, dew
+
+    def _encoded_buffers(self, B, n, H, W, numel, device):
+        """per chunk shape, like ``_buffers``: its events order the accesses to these too"""
+        key = (B, n, H, W, numel, str(device))
+        if key not in self._enc:
+            with torch.inference_mode(False):
+                self._enc[key] = ([torch.empty(numel, device=device) for _ in range(2)],
+                                  [torch.empty(numel, pin_memory=True) for _ in range(2)])
+        return self._enc[key]
+
     @torch.no_grad()
     def run(self, input_data, forcings, constants, on_chunk: Optional[Callable],
             forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
-            truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None):
+            truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None, encoder=None, init=None):
         if scorecard is not None and truth is None:          # (a host-side refusal, in front of the device checks)
             raise ValueError("Forecaster.run: a scorecard needs truth [B, n_stored, C, H, W] on the device")
         require_hip(input_data, forcings, constants)
@@ -339,8 +390,13 @@ class Forecaster:
         B, _, _, H, W = input_data.shape
         C, L = self.spec.num_channels, self.spec.num_levels
         truth_phys = self._check_verification(scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W)
+        init = self._check_encoder(encoder, init, B, C, L, H, W)
         n_chunk = min(n_stored, S if self.write_every_n is None else int(self.write_every_n))
-        dev, host, ddev, dhost, filled, copied, side, used = self._buffers(B, n_chunk, C, L, H, W, input_data.device)
+        dev, host, ddev, dhost, filled, copied, side, used = self._buffers(B, n_chunk, C, L, H, W, input_data.device,
+                                                                            pinned=encoder is None)
+        if encoder is not None:
+            from .encode import encode_chunk, pred_slice
+            enc, henc = self._encoded_buffers(B, n_chunk, H, W, encoder.numel(B, n_chunk + 1, H, W), input_data.device)
         main = torch.cuda.current_stream()
         const = constants[:, :1].permute(0, 1, 4, 2, 3)
         forc = forcings.permute(0, 1, 4, 2, 3)
@@ -364,12 +420,20 @@ class Forecaster:
                 return None if t is None else t.view(-1)[:B * n * ch * H * W].view(B, n, ch, H, W)
             return v(dev[j], C), v(host[j], C), v(ddev[j], L), v(dhost[j], L)
 
+        def slots(start, n):         # (n_td, td_off) of a chunk's encoded blocks: the first one carries the init state
+            return (n + 1, 1) if (start == 0 and init is not None) else (n, 0)
+
         def deliver(p):
             if on_chunk is None:
                 return
             j, start, n = p
-            _, h, _, dh = views(j, n)
             copied[j].synchronize()
+            if encoder is not None:
+                n_td, _ = slots(start, n)
+                on_chunk(variables=encoder.views(henc[j].numpy(), B, n_td, H, W), start_idx=start,
+                         pred_slice=pred_slice(start, n, with_init=init is not None))
+                return
+            _, h, _, dh = views(j, n)
             on_chunk(forecast=h.numpy(), start_idx=start, dewpoint=dh.numpy() if self.dewpoint else None)
 
         pending = None         # (buffer index, start_idx, n) enqueued for copy, not yet handed over
@@ -398,12 +462,21 @@ class Forecaster:
                 i_stored += 1
             if p.flush is not None:
                 start, n = p.flush
+                if encoder is not None:        # on the main stream, in front of `filled`, into the buffer `copied[k]` guards
+                    n_td, td_off = slots(start, n)
+                    if td_off:
+                        encode_chunk(init[0], init[1], encoder, enc[k], n_td, 0)
+                    encode_chunk(d, dd if encoder.dewpoint else None, encoder, enc[k], n_td, td_off)
+                    m = encoder.numel(B, n_td, H, W)
                 filled[k].record(main)
                 with torch.cuda.stream(side):
                     side.wait_event(filled[k])
-                    h.copy_(d, non_blocking=True)
-                    if self.dewpoint:
-                        dh.copy_(dd, non_blocking=True)
+                    if encoder is not None:
+                        henc[k][:m].copy_(enc[k][:m], non_blocking=True)
+                    else:
+                        h.copy_(d, non_blocking=True)
+                        if self.dewpoint:
+                            dh.copy_(dd, non_blocking=True)
                     copied[k].record(side)
                 used[k] = True
                 if pending is not None:
