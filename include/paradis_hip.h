@@ -448,6 +448,38 @@ int paradis_assemble_batch(const float* store, int64_t T, int F, int H, int W, c
                            int64_t interval_steps, const paradis_plane_t* planes, int n_time_inputs, int Fin, int S,
                            int Fout, float* input, float* target, float eps_q, int* flag, void* stream);
 
+/* ---- The 16-bit packed store (ABI 10, additive), csrc/feed.hip: GRIB simple packing per plane.  A plane is one
+ * (time, feature) field of P = H*W values.  domain [F] DEVICE int: 0 linear (y = x), 1 log (y = log(x + 1e-6), the
+ * precipitation normalisation's shift; log and exp evaluated in double and rounded to float32 once).  lo, hi: minimum
+ * and maximum of the plane's finite y; s = (hi - lo) / 65534 in float32.  Code 65535 is "missing": NaN and +-Inf are
+ * stored so and decode to NaN (the float32 store passes Inf through).  Otherwise code = rint((y - lo) / s) clamped to
+ * [0, 65534], 0 when s == 0; a plane without a finite value has lo = s = 0; a lo of -0 is stored as +0.  Decode:
+ * y' = lo + s * (float)code, two fp32 roundings and no FMA; log domain: x' = max((float)exp(y') - 1e-6f, 0).
+ * params: DEVICE float [T, F, 2] = (lo, s);  codes: DEVICE uint16 [T, F, H, W].
+ *
+ * paradis_pack_planes: slab [n, F, H, W] fp32 (dense) -> rows [row0, row0 + n) of codes and params.  Two launches: the
+ * minimum / maximum of pieces of paradis_pack_planes_piece() values into ws (paradis_pack_planes_ws_bytes(n, F, H, W)
+ * bytes, 4-byte aligned), then every workgroup folds its plane's partials and quantises its piece.  No atomics:
+ * bit-identical run to run, and a slab packed in pieces equals the slab packed whole.  n == 0 does nothing.
+ * Algorithmic HBM bytes: 10 per value (the slab is read twice).
+ * paradis_unpack_planes: rows [a, b) decoded to out [b - a, F, H, W] fp32.  a == b does nothing.  6 B per value.
+ * paradis_assemble_batch_packed: paradis_assemble_batch over a packed store - the same kernel over another element
+ * reader, the same plane table, clamping, flag, B == 0 and target == NULL; the decode is the one of
+ * paradis_unpack_planes, so its batch equals, bit for bit, paradis_assemble_batch over the unpacked rows.  6 B per value.
+ * 16-byte stores fed by 8-byte loads of four codes when H*W % 4 == 0, codes are 8-byte and the outputs (pack: the
+ * slab) 16-byte aligned; scalar otherwise, the same bits.  Every entry returns 1 before any HIP call for a bad shape,
+ * rows outside [0, T], a missing pointer or a grid above the launch limit. */
+int paradis_pack_planes_piece(void);
+size_t paradis_pack_planes_ws_bytes(int n, int F, int H, int W);
+int paradis_pack_planes(const float* slab, int n, int F, int H, int W, const int* domain, int64_t row0, int64_t T,
+                        uint16_t* codes, float* params, void* ws, void* stream);
+int paradis_unpack_planes(const uint16_t* codes, const float* params, const int* domain, int64_t T, int F, int H, int W,
+                          int64_t a, int64_t b, float* out, void* stream);
+int paradis_assemble_batch_packed(const uint16_t* codes, const float* params, const int* domain, int64_t T, int F,
+                                  int H, int W, const int64_t* idx, int B, int64_t base, int64_t interval_steps,
+                                  const paradis_plane_t* planes, int n_time_inputs, int Fin, int S, int Fout,
+                                  float* input, float* target, float eps_q, int* flag, void* stream);
+
 /* ---- f5: forecast post-processing (reference trainer.py:772-778 = utils/postprocessing.py:190-215 de-normalisation
  * + utils/postprocessing.py:74-122,143-187 Cartesian -> spherical winds, and the dew-point depression of
  * utils/mhuaes.py:33-96 that utils/file_output.py:165-173 derives - all on the CPU there).  One pass: reads the

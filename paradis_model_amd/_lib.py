@@ -58,6 +58,11 @@ SIGNATURES = {
     "paradis_normalize_features": (I, [P, P, P, P, L, I, ctypes.c_float, I, P]),
     "paradis_assemble_batch_chunk": (I, []),
     "paradis_assemble_batch": (I, [P, L, I, I, I, P, I, L, L, P, I, I, I, I, P, P, F, P, P]),
+    "paradis_pack_planes_piece": (I, []),
+    "paradis_pack_planes_ws_bytes": (S, [I, I, I, I]),
+    "paradis_pack_planes": (I, [P, I, I, I, I, P, L, L, P, P, P, P]),
+    "paradis_unpack_planes": (I, [P, P, P, L, I, I, I, L, L, P, P]),
+    "paradis_assemble_batch_packed": (I, [P, P, P, L, I, I, I, P, I, L, L, P, I, I, I, I, P, P, F, P, P]),
     "paradis_global_bias_m8_fwd": (I, [P, P, P, P, I, I, I, I, P]),
     "paradis_global_bias_m8_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P]),
     "paradis_global_bias_proj_bwd": (I, [P, P, P, P, P, I, I, L, P]),

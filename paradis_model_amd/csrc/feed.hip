@@ -186,16 +186,120 @@ normalize_kernel(float* __restrict__ data, const int* __restrict__ kind, const f
   data[i] = normalize_value(data[i], k, p0[c], p1[c], eps_q, inverse);
 }
 
+// 16-bit packed planes (GRIB simple packing; DESIGN.md, "The packed store").  A plane is one (time, feature) field of P
+// values; it carries (lo, s) in a float32 table [T, F, 2] and 16-bit codes, PACK_MISSING for NaN / +-Inf.  The packed
+// quantity of domain 1 (log) is y = log(x + 1e-6), the precipitation normalisation's own shift, of domain 0 (linear)
+// y = x.  log and exp are taken in double and rounded once: the correctly rounded float32 value, which every platform's
+// libm gives alike (logf / expf differ between libraries in the last bit, and a code would then depend on who packed).
+constexpr int PACK_MISSING = 65535;
+constexpr float PACK_TOP = 65534.0f;
+
+__device__ __forceinline__ float pack_domain_value(float x, int domain) {
+  return domain == 1 ? (float)log((double)(x + 1e-6f)) : x;
+}
+
+// the code of one packed-domain value; s == 0: a constant plane
+__device__ __forceinline__ uint32_t pack_code(float y, float lo, float s) {
+  if (!isfinite(y)) return PACK_MISSING;
+  const float c = s == 0.f ? 0.f : rintf((y - lo) / s);
+  return (uint32_t)fminf(fmaxf(c, 0.f), PACK_TOP);
+}
+
+// The ONE decode: unpack_planes_kernel and the packed assemble_batch_kernel both call it, so a batch assembled from a
+// packed store equals, bit for bit, the float32 batch assembled from the unpacked store.  Two fp32 roundings, no FMA.
+__device__ __forceinline__ float unpack_value(uint32_t code, float lo, float s, int domain) {
+  if (code == PACK_MISSING) return __builtin_nanf("");
+  const float y = lo + s * (float)code;
+  return domain == 1 ? fmaxf((float)exp((double)y) - 1e-6f, 0.f) : y;
+}
+
+// The element readers of the plane copy below: where a plane of the store starts, and four / one of its values.
+struct FloatPlanes {
+  const float* __restrict__ data;
+  struct Plane {
+    const float* __restrict__ p;
+  };
+  typedef float4 Quad;
+  __device__ __forceinline__ Plane plane(int64_t index, int /*f*/, int64_t P) const { return Plane{data + index * P}; }
+  static __device__ __forceinline__ Quad load_quad(const Plane& pl, int64_t i) {
+    return *reinterpret_cast<const float4*>(pl.p + i);
+  }
+  static __device__ __forceinline__ float4 quad_values(const Plane&, const Quad& q) { return q; }
+  static __device__ __forceinline__ float value(const Plane& pl, int64_t i) { return pl.p[i]; }
+};
+
+struct PackedPlanes {
+  const uint16_t* __restrict__ codes;
+  const float* __restrict__ params;     // [T, F, 2]: lo, s
+  const int* __restrict__ domain;       // [F]
+  struct Plane {
+    const uint16_t* __restrict__ p;
+    float lo, s;
+    int domain;
+  };
+  typedef uint2 Quad;                   // four codes: one 8-byte load
+  __device__ __forceinline__ Plane plane(int64_t index, int f, int64_t P) const {
+    return Plane{codes + index * P, params[2 * index], params[2 * index + 1], domain[f]};
+  }
+  static __device__ __forceinline__ Quad load_quad(const Plane& pl, int64_t i) {
+    return *reinterpret_cast<const uint2*>(pl.p + i);
+  }
+  static __device__ __forceinline__ float4 quad_values(const Plane& pl, const Quad& q) {
+    float4 o;
+    o.x = unpack_value(q.x & 0xffffu, pl.lo, pl.s, pl.domain);
+    o.y = unpack_value(q.x >> 16, pl.lo, pl.s, pl.domain);
+    o.z = unpack_value(q.y & 0xffffu, pl.lo, pl.s, pl.domain);
+    o.w = unpack_value(q.y >> 16, pl.lo, pl.s, pl.domain);
+    return o;
+  }
+  static __device__ __forceinline__ float value(const Plane& pl, int64_t i) {
+    return unpack_value(pl.p[i], pl.lo, pl.s, pl.domain);
+  }
+};
+
 // Batch assembly from a device-resident channels-first store [T, F, P] (P = H*W): one workgroup copies one chunk of
 // AB_CHUNK = AB_THREADS * 4 * AB_UNROLL values of ONE output plane through that plane's normalisation, so the table
 // entry, the sample's time row and both plane addresses are wave-uniform (scalar loads, no divergence in the kind
 // switch).  Planes [0, n_in) of a sample are the input's channels, [n_in, n_in + n_out) the target's (step-major).
-// 8 B of HBM traffic per value.  Rows and features outside the store are CLAMPED (never read outside) and reported
+// 8 B of HBM traffic per value from a float32 store, 6 B from a packed one (whose plane's lo / s / domain are
+// wave-uniform too).  Rows and features outside the store are CLAMPED (never read outside) and reported
 // through *flag; a negative or enormous idx[b] is limited first so that base + idx * interval cannot wrap.
 constexpr int AB_THREADS = 256, AB_UNROLL = 2, AB_CHUNK = AB_THREADS * 4 * AB_UNROLL;
 
+// values [lo, hi) of one plane through normalisation k (0: none).  vec: lo, hi and both plane bases are multiples of
+// four values, the destination 16-byte and the source Quad aligned.
+template <class Reader>
+__device__ __forceinline__ void copy_plane_chunk(const typename Reader::Plane& pl, float* __restrict__ dst, int64_t lo,
+                                                 int64_t hi, int k, float a, float c, float eps_q, int vec) {
+  if (vec) {
+    typename Reader::Quad q[AB_UNROLL];
+#pragma unroll
+    for (int u = 0; u < AB_UNROLL; ++u) {
+      const int64_t i = lo + (int64_t)(u * AB_THREADS + threadIdx.x) * 4;
+      if (i < hi) q[u] = Reader::load_quad(pl, i);
+    }
+#pragma unroll
+    for (int u = 0; u < AB_UNROLL; ++u) {
+      const int64_t i = lo + (int64_t)(u * AB_THREADS + threadIdx.x) * 4;
+      if (i < hi) {
+        const float4 v = Reader::quad_values(pl, q[u]);
+        float4 o;
+        o.x = normalize_value(v.x, k, a, c, eps_q, 0);
+        o.y = normalize_value(v.y, k, a, c, eps_q, 0);
+        o.z = normalize_value(v.z, k, a, c, eps_q, 0);
+        o.w = normalize_value(v.w, k, a, c, eps_q, 0);
+        *reinterpret_cast<float4*>(dst + i) = o;
+      }
+    }
+  } else {
+    for (int64_t i = lo + threadIdx.x; i < hi; i += AB_THREADS)
+      dst[i] = normalize_value(Reader::value(pl, i), k, a, c, eps_q, 0);
+  }
+}
+
+template <class Reader>
 __global__ void __launch_bounds__(AB_THREADS)
-assemble_batch_kernel(const float* __restrict__ store, int64_t T, int F, int64_t P, const int64_t* __restrict__ idx,
+assemble_batch_kernel(const Reader store, int64_t T, int F, int64_t P, const int64_t* __restrict__ idx,
                       int64_t base, int64_t interval, const paradis_plane_t* __restrict__ planes, int n_in, int n_out,
                       int chunks, float* __restrict__ input, float* __restrict__ target, float eps_q,
                       int* __restrict__ flag, int vec) {
@@ -212,34 +316,157 @@ assemble_batch_kernel(const float* __restrict__ store, int64_t T, int F, int64_t
   const int64_t row = row_raw < 0 ? 0 : (row_raw >= T ? T - 1 : row_raw);
   const int f = e.feature < 0 ? 0 : (e.feature >= F ? F - 1 : e.feature);
   if ((row != row_raw || f != e.feature) && threadIdx.x == 0) *flag = 1;
-  const float* __restrict__ src = store + (row * F + f) * P;
+  const typename Reader::Plane src = store.plane(row * F + f, f, P);
   float* __restrict__ dst = plane < n_in ? input + (b * n_in + plane) * P : target + (b * n_out + (plane - n_in)) * P;
   const int64_t lo = (int64_t)chunk * AB_CHUNK;
   const int64_t hi = lo + AB_CHUNK < P ? lo + AB_CHUNK : P;
-  const int k = e.kind;
-  const float a = e.p0, c = e.p1;
-  if (vec) {    // P % 4 == 0 and 16-byte aligned bases: lo, hi and every plane base are multiples of four floats
-    float4 q[AB_UNROLL];
+  copy_plane_chunk<Reader>(src, dst, lo, hi, e.kind, e.p0, e.p1, eps_q, vec);
+}
+
+// rows [a, b) of a packed store as float32: workgroup (plane, chunk) decodes one chunk of one plane
+__global__ void __launch_bounds__(AB_THREADS)
+unpack_planes_kernel(const PackedPlanes store, int F, int64_t P, int64_t first_plane, int chunks,
+                     float* __restrict__ out, int vec) {
+  const uint32_t blk = blockIdx.x, r = blk / (uint32_t)chunks;
+  const int chunk = (int)(blk - r * (uint32_t)chunks);
+  const int64_t index = first_plane + r;
+  const PackedPlanes::Plane src = store.plane(index, (int)(index % F), P);
+  const int64_t lo = (int64_t)chunk * AB_CHUNK;
+  const int64_t hi = lo + AB_CHUNK < P ? lo + AB_CHUNK : P;
+  copy_plane_chunk<PackedPlanes>(src, out + (int64_t)r * P, lo, hi, 0, 0.f, 0.f, 0.f, vec);
+}
+
+// Packing.  Workgroup (plane, piece) owns PACK_PIECE cells of one plane of the slab.  Pass 1 writes the minimum and the
+// maximum of the piece's finite packed-domain values to ws[(plane * pieces + piece) * 2]; pass 2 folds the plane's
+// partials again (every workgroup of the plane, the same values: a minimum does not depend on the order, and no
+// atomics take part), writes the plane's (lo, s) once and the codes of its piece.  8 + 2 B of HBM traffic per value.
+constexpr int PACK_THREADS = 256, PACK_PIECE = 8192;
+
+// minimum and maximum over the workgroup, in every thread
+__device__ __forceinline__ void block_min_max(float& mn, float& mx) {
+  __shared__ float red[2][PACK_THREADS / WAVE];
 #pragma unroll
-    for (int u = 0; u < AB_UNROLL; ++u) {
-      const int64_t i = lo + (int64_t)(u * AB_THREADS + threadIdx.x) * 4;
-      if (i < hi) q[u] = *reinterpret_cast<const float4*>(src + i);
-    }
+  for (int o = 32; o > 0; o >>= 1) {
+    mn = fminf(mn, __shfl_xor(mn, o, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = mn;
+    red[1][threadIdx.x >> 6] = mx;
+  }
+  __syncthreads();
+  mn = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+  mx = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(PACK_THREADS)
+pack_min_max_kernel(const float* __restrict__ slab, int F, int64_t P, const int* __restrict__ domain, int pieces,
+                    float* __restrict__ ws) {
+  const uint32_t blk = blockIdx.x, plane = blk / (uint32_t)pieces;
+  const int piece = (int)(blk - plane * (uint32_t)pieces);
+  const int dom = domain[plane % (uint32_t)F];
+  const float* __restrict__ x = slab + (int64_t)plane * P;
+  const int64_t lo = (int64_t)piece * PACK_PIECE;
+  const int64_t hi = lo + PACK_PIECE < P ? lo + PACK_PIECE : P;
+  float mn = INFINITY, mx = -INFINITY;
+  if (VEC) {      // P % 4 == 0 and a 16-byte aligned slab: every quad below hi is whole
+    for (int64_t i = lo + 4 * (int64_t)threadIdx.x; i < hi; i += 4 * PACK_THREADS) {
+      const float4 q = *reinterpret_cast<const float4*>(x + i);
+      const float v[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-    for (int u = 0; u < AB_UNROLL; ++u) {
-      const int64_t i = lo + (int64_t)(u * AB_THREADS + threadIdx.x) * 4;
-      if (i < hi) {
-        float4 o;
-        o.x = normalize_value(q[u].x, k, a, c, eps_q, 0);
-        o.y = normalize_value(q[u].y, k, a, c, eps_q, 0);
-        o.z = normalize_value(q[u].z, k, a, c, eps_q, 0);
-        o.w = normalize_value(q[u].w, k, a, c, eps_q, 0);
-        *reinterpret_cast<float4*>(dst + i) = o;
+      for (int k = 0; k < 4; ++k) {
+        const float y = pack_domain_value(v[k], dom);
+        if (isfinite(y)) mn = fminf(mn, y), mx = fmaxf(mx, y);
       }
     }
   } else {
-    for (int64_t i = lo + threadIdx.x; i < hi; i += AB_THREADS) dst[i] = normalize_value(src[i], k, a, c, eps_q, 0);
+    for (int64_t i = lo + threadIdx.x; i < hi; i += PACK_THREADS) {
+      const float y = pack_domain_value(x[i], dom);
+      if (isfinite(y)) mn = fminf(mn, y), mx = fmaxf(mx, y);
+    }
   }
+  block_min_max(mn, mx);
+  if (threadIdx.x == 0) {
+    ws[2 * (int64_t)blk] = mn;
+    ws[2 * (int64_t)blk + 1] = mx;
+  }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(PACK_THREADS)
+pack_quantize_kernel(const float* __restrict__ slab, int F, int64_t P, const int* __restrict__ domain, int pieces,
+                     const float* __restrict__ ws, uint16_t* __restrict__ codes, float* __restrict__ params) {
+  const uint32_t blk = blockIdx.x, plane = blk / (uint32_t)pieces;
+  const int piece = (int)(blk - plane * (uint32_t)pieces);
+  const int dom = domain[plane % (uint32_t)F];
+  float mn = INFINITY, mx = -INFINITY;
+  for (int j = threadIdx.x; j < pieces; j += PACK_THREADS) {
+    mn = fminf(mn, ws[2 * ((int64_t)plane * pieces + j)]);
+    mx = fmaxf(mx, ws[2 * ((int64_t)plane * pieces + j) + 1]);
+  }
+  block_min_max(mn, mx);
+  // no finite value: lo = s = 0, every code missing.  lo == 0 is stored as +0 whichever zero the minimum met.
+  float lo_y = 0.f, s = 0.f;
+  if (mn <= mx) {
+    lo_y = mn == 0.f ? 0.f : mn;
+    s = (mx - mn) / PACK_TOP;
+  }
+  if (piece == 0 && threadIdx.x == 0) {
+    params[2 * (int64_t)plane] = lo_y;
+    params[2 * (int64_t)plane + 1] = s;
+  }
+  const float* __restrict__ x = slab + (int64_t)plane * P;
+  uint16_t* __restrict__ out = codes + (int64_t)plane * P;
+  const int64_t lo = (int64_t)piece * PACK_PIECE;
+  const int64_t hi = lo + PACK_PIECE < P ? lo + PACK_PIECE : P;
+  if (VEC) {      // as above, and 8-byte aligned codes
+    for (int64_t i = lo + 4 * (int64_t)threadIdx.x; i < hi; i += 4 * PACK_THREADS) {
+      const float4 q = *reinterpret_cast<const float4*>(x + i);
+      uint2 o;
+      o.x = pack_code(pack_domain_value(q.x, dom), lo_y, s) | (pack_code(pack_domain_value(q.y, dom), lo_y, s) << 16);
+      o.y = pack_code(pack_domain_value(q.z, dom), lo_y, s) | (pack_code(pack_domain_value(q.w, dom), lo_y, s) << 16);
+      *reinterpret_cast<uint2*>(out + i) = o;
+    }
+  } else {
+    for (int64_t i = lo + threadIdx.x; i < hi; i += PACK_THREADS)
+      out[i] = (uint16_t)pack_code(pack_domain_value(x[i], dom), lo_y, s);
+  }
+}
+
+__host__ inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// the argument checks and the launch of both assembly entry points
+template <class Reader>
+int assemble_batch_launch(const char* name, const Reader& store, bool store_ok, bool store_vec, int64_t T, int F, int H,
+                          int W, const int64_t* idx, int B, int64_t base, int64_t interval_steps,
+                          const paradis_plane_t* planes, int n_time_inputs, int Fin, int S, int Fout, float* input,
+                          float* target, float eps_q, int* flag, void* stream) {
+  PD_REQUIRE(T >= 1 && F >= 1 && H >= 1 && W >= 1 && B >= 0, "%s: bad shape T=%lld F=%d H=%d W=%d B=%d", name,
+             (long long)T, F, H, W, B);
+  PD_REQUIRE(n_time_inputs >= 1, "%s: n_time_inputs=%d must be >= 1", name, n_time_inputs);
+  PD_REQUIRE(S >= 0, "%s: forecast steps S=%d must be >= 0", name, S);
+  PD_REQUIRE(Fin >= 1 && Fout >= 0, "%s: bad feature counts Fin=%d Fout=%d", name, Fin, Fout);
+  PD_REQUIRE(interval_steps >= 1, "%s: interval_steps=%lld must be >= 1", name, (long long)interval_steps);
+  PD_REQUIRE((int64_t)n_time_inputs * Fin < (1 << 24) && (int64_t)S * Fout < (1 << 24),
+             "%s: too many planes per sample", name);
+  PD_REQUIRE(planes != nullptr, "%s: plane table required", name);
+  if (B == 0) return 0;
+  PD_REQUIRE(store_ok && idx != nullptr && input != nullptr && flag != nullptr,
+             "%s: store, idx, input and flag pointers required", name);
+  const int n_in = n_time_inputs * Fin;
+  const int n_out = target != nullptr ? S * Fout : 0;     // no target: the prediction-stage item
+  const int64_t P = (int64_t)H * W;
+  const int64_t chunks = ceil_div64(P, AB_CHUNK);
+  PD_REQUIRE(chunks < (1ll << 31), "%s: grid too large", name);
+  const int64_t blocks = (int64_t)B * (n_in + n_out) * chunks;
+  PD_REQUIRE(blocks < (1ll << 31), "%s: too large (%lld workgroups)", name, (long long)blocks);
+  const int vec = P % 4 == 0 && store_vec && aligned16(input) && (target == nullptr || aligned16(target));
+  hipLaunchKernelGGL(assemble_batch_kernel<Reader>, dim3((unsigned)blocks), dim3(AB_THREADS), 0, (hipStream_t)stream,
+                     store, T, F, P, idx, base, interval_steps, planes, n_in, n_out, (int)chunks, input, target, eps_q,
+                     flag, vec);
+  PD_CHECK_LAUNCH(name);
+  return 0;
 }
 
 }  // namespace
@@ -299,28 +526,77 @@ extern "C" int paradis_assemble_batch(const float* store, int64_t T, int F, int 
                                       int64_t base, int64_t interval_steps, const paradis_plane_t* planes,
                                       int n_time_inputs, int Fin, int S, int Fout, float* input, float* target,
                                       float eps_q, int* flag, void* stream) {
-  PD_REQUIRE(T >= 1 && F >= 1 && H >= 1 && W >= 1 && B >= 0, "assemble_batch: bad shape T=%lld F=%d H=%d W=%d B=%d",
-             (long long)T, F, H, W, B);
-  PD_REQUIRE(n_time_inputs >= 1, "assemble_batch: n_time_inputs=%d must be >= 1", n_time_inputs);
-  PD_REQUIRE(S >= 0, "assemble_batch: forecast steps S=%d must be >= 0", S);
-  PD_REQUIRE(Fin >= 1 && Fout >= 0, "assemble_batch: bad feature counts Fin=%d Fout=%d", Fin, Fout);
-  PD_REQUIRE(interval_steps >= 1, "assemble_batch: interval_steps=%lld must be >= 1", (long long)interval_steps);
-  PD_REQUIRE((int64_t)n_time_inputs * Fin < (1 << 24) && (int64_t)S * Fout < (1 << 24),
-             "assemble_batch: too many planes per sample");
-  PD_REQUIRE(planes != nullptr, "assemble_batch: plane table required");
-  if (B == 0) return 0;
-  PD_REQUIRE(store != nullptr && idx != nullptr && input != nullptr && flag != nullptr,
-             "assemble_batch: store, idx, input and flag pointers required");
-  const int n_in = n_time_inputs * Fin;
-  const int n_out = target != nullptr ? S * Fout : 0;     // no target: the prediction-stage item
+  return assemble_batch_launch("assemble_batch", FloatPlanes{store}, store != nullptr, aligned16(store), T, F, H, W, idx,
+                               B, base, interval_steps, planes, n_time_inputs, Fin, S, Fout, input, target, eps_q, flag,
+                               stream);
+}
+
+extern "C" int paradis_assemble_batch_packed(const uint16_t* codes, const float* params, const int* domain, int64_t T,
+                                             int F, int H, int W, const int64_t* idx, int B, int64_t base,
+                                             int64_t interval_steps, const paradis_plane_t* planes, int n_time_inputs,
+                                             int Fin, int S, int Fout, float* input, float* target, float eps_q,
+                                             int* flag, void* stream) {
+  return assemble_batch_launch("assemble_batch_packed", PackedPlanes{codes, params, domain},
+                               codes != nullptr && params != nullptr && domain != nullptr, aligned8(codes), T, F, H, W,
+                               idx, B, base, interval_steps, planes, n_time_inputs, Fin, S, Fout, input, target, eps_q,
+                               flag, stream);
+}
+
+extern "C" int paradis_pack_planes_piece(void) { return PACK_PIECE; }
+
+extern "C" size_t paradis_pack_planes_ws_bytes(int n, int F, int H, int W) {
+  if (n < 1 || F < 1 || H < 1 || W < 1) return 0;
+  return (size_t)n * (size_t)F * (size_t)ceil_div64((int64_t)H * W, PACK_PIECE) * 2 * sizeof(float);
+}
+
+extern "C" int paradis_pack_planes(const float* slab, int n, int F, int H, int W, const int* domain, int64_t row0,
+                                   int64_t T, uint16_t* codes, float* params, void* ws, void* stream) {
+  PD_REQUIRE(n >= 0 && F >= 1 && H >= 1 && W >= 1, "pack_planes: bad shape n=%d F=%d H=%d W=%d", n, F, H, W);
+  PD_REQUIRE(row0 >= 0 && T >= 1 && row0 <= T && (int64_t)n <= T - row0,
+             "pack_planes: rows [%lld, %lld) outside a store of %lld", (long long)row0, (long long)row0 + n,
+             (long long)T);
+  if (n == 0) return 0;
+  PD_REQUIRE(slab != nullptr && domain != nullptr && codes != nullptr && params != nullptr && ws != nullptr,
+             "pack_planes: slab, domain, codes, params and workspace pointers required");
+  const int64_t P = (int64_t)H * W;
+  const int64_t pieces = ceil_div64(P, PACK_PIECE);
+  const int64_t blocks = (int64_t)n * F * pieces;
+  PD_REQUIRE(pieces < (1ll << 31) && blocks < (1ll << 31), "pack_planes: too large (%lld workgroups)",
+             (long long)blocks);
+  uint16_t* out = codes + row0 * F * P;
+  float* par = params + row0 * F * 2;
+  hipStream_t st = (hipStream_t)stream;
+  const bool vec = P % 4 == 0 && aligned16(slab);
+  const dim3 grid((unsigned)blocks), block(PACK_THREADS);
+  if (vec) hipLaunchKernelGGL(pack_min_max_kernel<true>, grid, block, 0, st, slab, F, P, domain, (int)pieces, (float*)ws);
+  else hipLaunchKernelGGL(pack_min_max_kernel<false>, grid, block, 0, st, slab, F, P, domain, (int)pieces, (float*)ws);
+  if (vec && aligned8(out))
+    hipLaunchKernelGGL(pack_quantize_kernel<true>, grid, block, 0, st, slab, F, P, domain, (int)pieces,
+                       (const float*)ws, out, par);
+  else
+    hipLaunchKernelGGL(pack_quantize_kernel<false>, grid, block, 0, st, slab, F, P, domain, (int)pieces,
+                       (const float*)ws, out, par);
+  PD_CHECK_LAUNCH("pack_planes");
+  return 0;
+}
+
+extern "C" int paradis_unpack_planes(const uint16_t* codes, const float* params, const int* domain, int64_t T, int F,
+                                     int H, int W, int64_t a, int64_t b, float* out, void* stream) {
+  PD_REQUIRE(T >= 1 && F >= 1 && H >= 1 && W >= 1, "unpack_planes: bad shape T=%lld F=%d H=%d W=%d", (long long)T, F, H,
+             W);
+  PD_REQUIRE(a >= 0 && a <= b && b <= T, "unpack_planes: rows [%lld, %lld) outside a store of %lld", (long long)a,
+             (long long)b, (long long)T);
+  if (a == b) return 0;
+  PD_REQUIRE(codes != nullptr && params != nullptr && domain != nullptr && out != nullptr,
+             "unpack_planes: codes, params, domain and out pointers required");
   const int64_t P = (int64_t)H * W;
   const int64_t chunks = ceil_div64(P, AB_CHUNK);
-  PD_REQUIRE(chunks < (1ll << 31), "assemble_batch: grid too large");
-  const int64_t blocks = (int64_t)B * (n_in + n_out) * chunks;
-  PD_REQUIRE(blocks < (1ll << 31), "assemble_batch: too large (%lld workgroups)", (long long)blocks);
-  const int vec = P % 4 == 0 && aligned16(store) && aligned16(input) && (target == nullptr || aligned16(target));
-  hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)blocks), dim3(AB_THREADS), 0, (hipStream_t)stream, store, T,
-                     F, P, idx, base, interval_steps, planes, n_in, n_out, (int)chunks, input, target, eps_q, flag, vec);
-  PD_CHECK_LAUNCH("assemble_batch");
+  const int64_t blocks = (b - a) * F * chunks;
+  PD_REQUIRE(chunks < (1ll << 31) && blocks < (1ll << 31), "unpack_planes: too large (%lld workgroups)",
+             (long long)blocks);
+  const int vec = P % 4 == 0 && aligned8(codes) && aligned16(out);
+  hipLaunchKernelGGL(unpack_planes_kernel, dim3((unsigned)blocks), dim3(AB_THREADS), 0, (hipStream_t)stream,
+                     PackedPlanes{codes, params, domain}, F, P, a * F, (int)chunks, out, vec);
+  PD_CHECK_LAUNCH("unpack_planes");
   return 0;
 }

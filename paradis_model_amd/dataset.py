@@ -10,6 +10,10 @@ Restated from the reference: the feature bookkeeping of ``ERA5Dataset.__init__``
 of ``_getitem_standard`` / ``_getitem_prediction`` (``:337-423``) and the tables of ``_prepare_normalization``
 (``:458-544``).  Reading zarr / xarray is out of scope: the store arrives as an array the user has already read.
 
+``DeviceStore(packing="u16")`` holds the store as 16-bit codes with a float32 reference value and step per (time,
+feature) plane - half the bytes - packed slab by slab on the device (``paradis_pack_planes``) and decoded inside the same
+assembly launch (``paradis_assemble_batch_packed``); ``assemble_planes`` is the one place that chooses the entry point.
+
 No CPU fallback: ``batch()`` needs the store on the HIP device.  A store built with ``device="cpu"`` serves the host
 bookkeeping only (names, counts, tables, lengths).
 """
@@ -30,6 +34,66 @@ EPS_Q = 1e-12                       # era5_dataset.py:58
 SLAB_BYTES = 256 << 20              # host-to-device upload granularity of DeviceStore
 # one row of paradis_plane_t (include/paradis_hip.h)
 PLANE_DTYPE = np.dtype([("feature", "<i4"), ("dt", "<i4"), ("kind", "<i4"), ("p0", "<f4"), ("p1", "<f4")])
+# the packed store (include/paradis_hip.h, "The 16-bit packed store"): per-feature domain of the packed quantity
+DOMAIN_LINEAR, DOMAIN_LOG = 0, 1
+PACK_MISSING = 65535
+
+
+def _base_name(feature: str) -> str:
+    """"temperature_h500" -> "temperature" (era5_dataset.py:469)"""
+    return re.sub(r"_h\d+$", "", feature)
+
+
+def pack_planes(slab: torch.Tensor, row0: int, codes: torch.Tensor, params: torch.Tensor, domain: torch.Tensor,
+                ws_cache: Optional[dict] = None) -> None:
+    """``paradis_pack_planes``: the float32 slab ``[n, F, H, W]`` into rows ``[row0, row0 + n)`` of ``codes``
+    ``[T, F, H, W]`` (16-bit) and ``params`` ``[T, F, 2]``; ``domain``: device int32 ``[F]``."""
+    from ._tables import workspace
+    require_hip(slab, params)
+    n, F, H, W = (int(v) for v in slab.shape)
+    T = int(codes.shape[0])
+    if tuple(codes.shape[1:]) != (F, H, W) or tuple(params.shape) != (T, F, 2) or domain.numel() != F:
+        raise ValueError("pack_planes: slab, codes, params and domain disagree in shape")
+    if codes.element_size() != 2 or domain.dtype != torch.int32 or not codes.is_cuda or not domain.is_cuda:
+        raise ValueError("pack_planes: codes must be 16-bit and domain int32, both on the device")
+    if not (slab.is_contiguous() and codes.is_contiguous() and params.is_contiguous()):
+        raise ValueError("pack_planes: slab, codes and params must be contiguous")
+    ws = workspace({} if ws_cache is None else ws_cache, slab.device, lib.paradis_pack_planes_ws_bytes(n, F, H, W))
+    check(lib.paradis_pack_planes(dptr(slab), n, F, H, W, dptr(domain), int(row0), T, dptr(codes), dptr(params),
+                                  dptr(ws), stream_ptr()), "pack_planes")
+
+
+def unpack_planes(codes: torch.Tensor, params: torch.Tensor, domain: torch.Tensor, a: int, b: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``paradis_unpack_planes``: rows ``[a, b)`` of a packed store as float32 ``[b - a, F, H, W]``"""
+    T, F, H, W = (int(v) for v in codes.shape)
+    a, b = int(a), int(b)
+    if not 0 <= a <= b <= T:
+        raise IndexError(f"unpack_planes: rows [{a}, {b}) outside a store of {T}")
+    if out is None:
+        out = torch.empty(b - a, F, H, W, dtype=torch.float32, device=codes.device)
+    require_hip(out, params)
+    if tuple(out.shape) != (b - a, F, H, W) or not out.is_contiguous():
+        raise ValueError(f"unpack_planes: out must be contiguous [{b - a}, {F}, {H}, {W}]")
+    check(lib.paradis_unpack_planes(dptr(codes), dptr(params), dptr(domain), T, F, H, W, a, b, dptr(out), stream_ptr()),
+          "unpack_planes")
+    return out
+
+
+def assemble_planes(store: "DeviceStore", idx: torch.Tensor, base: int, interval_steps: int, planes: torch.Tensor,
+                    n_time_inputs: int, Fin: int, S: int, Fout: int, inp: torch.Tensor, tgt: Optional[torch.Tensor],
+                    flag: torch.Tensor) -> None:
+    """The batch-assembly launch over whatever the store holds: ``paradis_assemble_batch`` for a float32 store,
+    ``paradis_assemble_batch_packed`` for a packed one - the one place that chooses."""
+    T, F, H, W = store.shape
+    require_hip(store.data if store.packing is None else store.plane_params, inp, tgt)
+    tail = (T, F, H, W, dptr(idx), int(idx.numel()), int(base), int(interval_steps), dptr(planes), n_time_inputs, Fin, S,
+            Fout, dptr(inp), dptr(tgt), EPS_Q, dptr(flag), stream_ptr())
+    if store.packing is None:
+        check(lib.paradis_assemble_batch(dptr(store.data), *tail), "assemble_batch")
+    else:
+        check(lib.paradis_assemble_batch_packed(dptr(store.codes), dptr(store.plane_params), dptr(store.domain_dev),
+                                                *tail), "assemble_batch_packed")
 
 
 def _hours(text) -> int:
@@ -46,10 +110,22 @@ class DeviceStore:
     reference's ``stats`` store), or None: computed from the uploaded data (``prepare.store_statistics``).  lat_deg [H]
     ascending, lon_deg [W].  constants: the [H, W, Cc] tensor the reference's dataset precomputes (``:193-251``).
     toa_mean / toa_std: ``toa_radiation_mean / _std`` of the stats store, or None: computed from ``times`` and the grid
-    (``prepare.toa_radiation_stats``).  Computing either needs the HIP device."""
+    (``prepare.toa_radiation_stats``).  Computing either needs the HIP device.
+
+    packing: None - ``data`` is the float32 store - or "u16": the store is held as 16-bit codes ``codes`` [T, F, H, W]
+    with a ``(lo, step)`` pair per (time, feature) plane in ``plane_params`` [T, F, 2] (GRIB simple packing, half the
+    bytes; DESIGN.md "The packed store"), ``data`` is None, and batches are decoded inside the assembly launch.
+    log_packed: base names (``_h<level>`` stripped) of the features packed as ``log(x + 1e-6)``; ``domain`` [F] says
+    which.  NaN and +-Inf are stored as "missing" and come back as NaN.  Each uploaded slab passes through one float32
+    staging buffer of ``SLAB_BYTES``; with ``stats=None`` the statistics are taken from that slab before it is packed,
+    so from the original values.  ``rows(a, b)`` gives physical float32 values of either kind of store."""
 
     def __init__(self, data, times, features: Sequence[str], stats, lat_deg, lon_deg, constants, toa_mean=None,
-                 toa_std=None, device="cuda"):
+                 toa_std=None, device="cuda", packing=None, log_packed=("total_precipitation_6hr",)):
+        if packing not in (None, "u16"):
+            raise ValueError(f"DeviceStore: packing must be None or 'u16', got {packing!r}")
+        if packing is not None and torch.device(device).type == "cpu":
+            raise ValueError("DeviceStore: a packed store is packed and read on the HIP device (no CPU fallback)")
         if len(data.shape) != 4:
             raise ValueError(f"DeviceStore: data must be [T, F, H, W], got {tuple(data.shape)}")
         T, F, H, W = (int(v) for v in data.shape)
@@ -98,17 +174,63 @@ class DeviceStore:
             raise ValueError(f"DeviceStore: constants must be [H, W, Cc], got {tuple(const.shape)}")
         self.constants = const.to(device=self.device, dtype=torch.float32).contiguous()
         self.times_dev = self.times_us.to(self.device)
-        self.data = torch.empty(T, F, H, W, dtype=torch.float32, device=self.device)
+        self.packing = packing
+        log_names = {str(n) for n in log_packed}
+        self.domain = np.array([DOMAIN_LOG if packing is not None and _base_name(f) in log_names else DOMAIN_LINEAR
+                                for f in self.features], dtype=np.int32)
         rows = max(1, SLAB_BYTES // max(1, F * H * W * 4))
-        for a in range(0, T, rows):
-            slab = data[a:a + rows]
-            if not isinstance(slab, torch.Tensor):
-                slab = torch.from_numpy(np.ascontiguousarray(slab))
-            self.data[a:a + rows].copy_(slab)
-        if stats is None:
-            from .prepare import store_statistics
-            res = store_statistics(self.data)
-            self.stats = {key: res[key] for key in ("mean", "std", "min", "max")}
+        if packing is None:
+            self.codes = self.plane_params = self.domain_dev = None
+            self.data = torch.empty(T, F, H, W, dtype=torch.float32, device=self.device)
+            for a in range(0, T, rows):
+                self.data[a:a + rows].copy_(self._host_slab(data, a, rows))
+            if stats is None:
+                from .prepare import store_statistics
+                res = store_statistics(self.data)
+                self.stats = {key: res[key] for key in ("mean", "std", "min", "max")}
+        else:
+            from .prepare import StoreStats
+            self.data = None
+            self.domain_dev = torch.from_numpy(self.domain).to(self.device)
+            self.codes = torch.empty(T, F, H, W, dtype=torch.uint16, device=self.device)
+            self.plane_params = torch.empty(T, F, 2, dtype=torch.float32, device=self.device)
+            staging = torch.empty(min(rows, T), F, H, W, dtype=torch.float32, device=self.device)
+            acc = StoreStats(F, H, W, device=self.device) if stats is None else None
+            ws = {}
+            for a in range(0, T, rows):
+                slab = self._host_slab(data, a, rows)
+                on_dev = staging[:slab.shape[0]].copy_(slab)
+                if acc is not None:
+                    acc.update(on_dev)
+                pack_planes(on_dev, a, self.codes, self.plane_params, self.domain_dev, ws)
+            if acc is not None:
+                res = acc.result()
+                self.stats = {key: res[key] for key in ("mean", "std", "min", "max")}
+
+    @staticmethod
+    def _host_slab(data, a, rows):
+        slab = data[a:a + rows]
+        if not isinstance(slab, torch.Tensor):
+            slab = torch.from_numpy(np.ascontiguousarray(slab))
+        return slab
+
+    @property
+    def nbytes(self) -> int:
+        """device bytes of the stored fields (codes and plane parameters, or the float32 array)"""
+        if self.packing is None:
+            return self.data.numel() * 4
+        return self.codes.numel() * 2 + self.plane_params.numel() * 4
+
+    def rows(self, a: int, b: int) -> torch.Tensor:
+        """time rows ``[a, b)`` in physical units, float32 ``[b - a, F, H, W]``: a view of a float32 store, a decoded
+        copy (``paradis_unpack_planes``) of a packed one"""
+        T = self.shape[0]
+        a, b = int(a), int(b)
+        if not 0 <= a <= b <= T:
+            raise IndexError(f"DeviceStore.rows: rows [{a}, {b}) outside a store of {T}")
+        if self.packing is None:
+            return self.data[a:b]
+        return unpack_planes(self.codes, self.plane_params, self.domain_dev, a, b)
 
     def row_of(self, when_us: int, side: str = "left") -> int:
         """first store row at or after (``left``) / after (``right``) the given time"""
@@ -237,7 +359,7 @@ class DeviceDataset:
 
     # ------------------------------------------------------------------ tables
     def _kind_of(self, feature: str) -> int:
-        name = re.sub(r"_h\d+$", "", feature)           # era5_dataset.py:469-477
+        name = _base_name(feature)                      # era5_dataset.py:469-477
         if self.custom_normalization and name == "total_precipitation_6hr":
             return KIND_PRECIP
         if self.custom_normalization and name == "specific_humidity":
@@ -302,12 +424,8 @@ class DeviceDataset:
     def assemble(self, idx: torch.Tensor, inp: torch.Tensor, tgt: Optional[torch.Tensor]) -> None:
         """The one launch: input and (unless ``tgt`` is None) target of the samples ``idx`` (device int64) into the given
         contiguous float32 tensors.  No checks beyond the C entry point's: ``batch`` is the public way in."""
-        require_hip(self.store.data, inp, tgt)
-        T, F, H, W = self.store.shape
-        check(lib.paradis_assemble_batch(dptr(self.store.data), T, F, H, W, dptr(idx), int(idx.numel()), self.base,
-                                         self.interval_steps, dptr(self._planes), self.n_time_inputs,
-                                         self.num_dyn_inputs_single, self.forecast_steps, self.num_out_features,
-                                         dptr(inp), dptr(tgt), EPS_Q, dptr(self._flag), stream_ptr()), "assemble_batch")
+        assemble_planes(self.store, idx, self.base, self.interval_steps, self._planes, self.n_time_inputs,
+                        self.num_dyn_inputs_single, self.forecast_steps, self.num_out_features, inp, tgt, self._flag)
 
     def batch(self, indices, out=None):
         """(input [B,1,n_t*Fin,H,W], target [B,S,Fout,H,W], forcings [B,S,H,W,Nf], constants [B,1,H,W,Cc]) of the samples

@@ -275,7 +275,7 @@ def initial_state(dataset, indices, post_spec, lat_deg, lon_deg):
     dataset: a ``dataset.DeviceDataset``; post_spec: the forecaster's ``PostSpec`` (its names are the dataset's output
     features).  Runs once per run: composed from the batch-assembly launch (a gather without normalisation) and the
     post-processing launch, no kernel of its own."""
-    from .dataset import EPS_Q, PLANE_DTYPE
+    from .dataset import PLANE_DTYPE, assemble_planes
     from .forecast import postprocess
     if list(post_spec.names) != list(dataset.dyn_output_features):
         raise ValueError("initial_state: the PostSpec's names are not the dataset's output features")
@@ -298,9 +298,7 @@ def initial_state(dataset, indices, post_spec, lat_deg, lon_deg):
         dew = torch.empty(B, 1, L, H, W, dtype=torch.float32, device=dev) if post_spec.dewpoint else None
         if B == 0:
             return state, dew
-        check(lib.paradis_assemble_batch(dptr(store.data), T, F, H, W, dptr(idx), B, dataset.base,
-                                         dataset.interval_steps, dptr(planes), 1, C, 0, 0, dptr(raw), None, EPS_Q,
-                                         dptr(dataset._flag), stream_ptr()), "assemble_batch")
+        assemble_planes(store, idx, dataset.base, dataset.interval_steps, planes, 1, C, 0, 0, raw, None, dataset._flag)
         if missing:
             raw[:, missing] = float("nan")
         spec0 = dataclasses.replace(post_spec, kind=np.zeros_like(post_spec.kind), _dev={})

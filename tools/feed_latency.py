@@ -12,9 +12,15 @@ The store is sized past the 256 MiB Infinity Cache and every call takes another 
 come from HBM.  Every configuration runs in a child process of its own under its own time limit; after a child that
 failed or ran out of time nothing more is started.
 
-One JSON line, also written to profiles/feed_latency.json.  No thresholds: a measurement.
+``--packing u16`` adds the packed store (``DeviceStore(packing="u16")``) of the same data in the same process, its
+calls alternated with the float ones: the packed assembly launch and a whole ``batch()`` from it
+(``packed_over_float_assemble`` = packed / float assembly time; by bytes 6 / 8), and on one upload slab
+(``dataset.SLAB_BYTES`` of float32 rows) the pack launch, the unpack launch and an ATen ``copy_`` of the slab.
 
-    python tools/feed_latency.py [--rounds 5] [--limit 240]
+One JSON line, also written to profiles/feed_latency.json (profiles/feed_latency_u16.json with ``--packing``).  No
+thresholds: a measurement.
+
+    python tools/feed_latency.py [--rounds 5] [--limit 240] [--packing u16]
 """
 import argparse
 import json
@@ -54,7 +60,18 @@ def build(H, W, T, S):
     n_t = cfg.dataset.n_time_inputs
     start = str(times[n_t - 1].astype("datetime64[s]"))
     end = str(times[T - 1 - S].astype("datetime64[s]"))
-    return DeviceDataset(store, cfg, start, end, S)
+    ds = DeviceDataset(store, cfg, start, end, S)
+    ds.span = (start, end)
+    return ds
+
+
+def packed_twin(ds, packing):
+    """the dataset of ``ds`` over a packed store of the same values"""
+    from paradis_model_amd.dataset import DeviceDataset, DeviceStore
+    st = ds.store
+    store = DeviceStore(st.data, st.times_us, st.features, st.stats, st.lat, st.lon, st.constants, st.toa_mean,
+                        st.toa_std, device=st.device, packing=packing)
+    return DeviceDataset(store, ds.cfg, *ds.span, ds.forecast_steps)
 
 
 def composed(ds, idx):
@@ -89,7 +106,7 @@ def event_ms(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
-def measure(H, W, B, S, T, iters, rounds):
+def measure(H, W, B, S, T, iters, rounds, packing=None):
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("feed_latency.py needs the GPU")
@@ -117,6 +134,20 @@ def measure(H, W, B, S, T, iters, rounds):
            "assemble": lambda: ds.assemble(next_idx(), out[0], out[1]),
            "composed": lambda: composed(ds, next_idx()),
            "copy": lambda: dst.copy_(src)}
+    if packing:
+        from paradis_model_amd import dataset as D
+        pds = packed_twin(ds, packing)
+        ps = pds.store
+        F = ps.shape[1]
+        n = min(T, max(1, D.SLAB_BYTES // (F * H * W * 4)))                # the rows of one upload slab
+        slab, stage = ds.store.data[:n], torch.empty(n, F, H, W, device=dev)
+        codes, params = torch.empty_like(ps.codes[:n]), torch.empty_like(ps.plane_params[:n])
+        ws = {}
+        fns.update({"assemble_packed": lambda: pds.assemble(next_idx(), out[0], out[1]),
+                    "batch_packed": lambda: pds.batch(next_idx(), out=out),
+                    "pack": lambda: D.pack_planes(slab, 0, codes, params, ps.domain_dev, ws),
+                    "unpack": lambda: D.unpack_planes(ps.codes, ps.plane_params, ps.domain_dev, 0, n, out=stage),
+                    "slab_copy": lambda: stage.copy_(slab)})
     with torch.no_grad():
         for fn in fns.values():
             for _ in range(3):
@@ -131,6 +162,20 @@ def measure(H, W, B, S, T, iters, rounds):
     same = all(torch.equal(a, b) for a, b in zip(got, ref))
     med = {k: statistics.median(v) for k, v in ms.items()}
     nbytes = 8.0 * n_values
+    extra = {}
+    if packing:
+        slab_values = slab.numel()
+        extra = {"packing": packing, "packed_store_GB": round(ps.nbytes / 1e9, 3),
+                 "assemble_packed_ms": round(med["assemble_packed"], 5), "batch_packed_ms": round(med["batch_packed"], 5),
+                 "packed_over_float_assemble": round(med["assemble_packed"] / med["assemble"], 3),
+                 "packed_over_float_batch": round(med["batch_packed"] / med["batch"], 3),
+                 "assemble_packed_TBps": round(6.0 * n_values / (med["assemble_packed"] * 1e-3) / 1e12, 3),
+                 "slab_rows": n, "slab_MB": round(4.0 * slab_values / 1e6, 2), "pack_ms": round(med["pack"], 5),
+                 "unpack_ms": round(med["unpack"], 5), "slab_copy_ms": round(med["slab_copy"], 5),
+                 "pack_Gvalues_per_s": round(slab_values / (med["pack"] * 1e-3) / 1e9, 2),
+                 "unpack_Gvalues_per_s": round(slab_values / (med["unpack"] * 1e-3) / 1e9, 2),
+                 "slab_copy_Gvalues_per_s": round(slab_values / (med["slab_copy"] * 1e-3) / 1e9, 2),
+                 "pack_over_slab_copy": round(med["pack"] / med["slab_copy"], 3)}
     return {"device": torch.cuda.get_device_name(0), "grid": f"{H}x{W}", "B": B, "S": S, "store_times": T,
             "store_GB": round(ds.store.data.numel() * 4 / 1e9, 3), "iters": iters, "rounds": rounds,
             "batch_ms": round(med["batch"], 5), "assemble_ms": round(med["assemble"], 5),
@@ -140,24 +185,29 @@ def measure(H, W, B, S, T, iters, rounds):
             "copy_TBps": round(nbytes / (med["copy"] * 1e-3) / 1e12, 3),
             "fraction_of_copy_rate": round(med["copy"] / med["assemble"], 3),
             "composed_over_batch": round(med["composed"] / med["batch"], 2),
-            "batch_equals_composed": bool(same), "index_errors": ds.index_errors()}
+            "batch_equals_composed": bool(same), "index_errors": ds.index_errors(), **extra}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="time limit of each configuration's child process, seconds")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "feed_latency.json"))
+    ap.add_argument("--packing", default=None, choices=["u16"], help="also measure the packed store of the same data")
+    ap.add_argument("--out", default=None, help="default profiles/feed_latency.json, feed_latency_u16.json with --packing")
     ap.add_argument("--one", default="", help="(internal) H,W,B,S,T,iters: measure one configuration, print JSON")
     a = ap.parse_args()
     if a.one:
         H, W, B, S, T, iters = (int(v) for v in a.one.split(","))
-        print("RESULT " + json.dumps(measure(H, W, B, S, T, iters, a.rounds)), flush=True)
+        print("RESULT " + json.dumps(measure(H, W, B, S, T, iters, a.rounds, a.packing)), flush=True)
         return
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "feed_latency_u16.json" if a.packing else "feed_latency.json")
     res = {"tool": "feed_latency", "configs": []}
     for cfg in CONFIGS:
         tag = "x".join(str(v) for v in cfg[:4])
         cmd = [sys.executable, os.path.abspath(__file__), "--rounds", str(a.rounds), "--one", ",".join(str(v) for v in cfg)]
+        if a.packing:
+            cmd += ["--packing", a.packing]
         try:
             out = subprocess.run(cmd, timeout=a.limit, capture_output=True, text=True)
         except subprocess.TimeoutExpired:
