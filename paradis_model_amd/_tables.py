@@ -8,6 +8,7 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 
 def chunk_list(numels: Sequence[int], chunk: int, tensors=None) -> Tuple[List[int], List[int]]:
@@ -87,6 +88,28 @@ def dense_state(t: torch.Tensor, what: str, who: str, fp32: bool = False) -> Non
             raise ValueError(f"{who}: {what} must be float32 with dense [C, H, W] states")
     elif not dense:
         raise ValueError(f"{who}: {what} must hold dense [C, H, W] states")
+
+
+def batch_stride(t: torch.Tensor, dense: int) -> int:
+    """``t.stride(0)``, or ``dense`` when the batch axis has one entry (the stride of such an axis is arbitrary)"""
+    return t.stride(0) if t.shape[0] > 1 else dense
+
+
+def device_tables(cache: dict, key, device, arrays) -> tuple:
+    """``cache[key]`` = the numpy ``arrays`` as a tuple of tensors on ``device``, made outside inference mode so that every
+    later mode may read them.  For a miss: a launch-bound owner looks first (``cache.get(key) or device_tables(...)``)."""
+    with torch.inference_mode(False):
+        cache[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in arrays)
+    return cache[key]
+
+
+def sum_over_ranks(t: torch.Tensor, sync_dist: bool) -> torch.Tensor:
+    """``t`` on the host: with ``sync_dist`` and an initialised process group summed over the ranks by ONE all-reduce
+    first (under gloo after the one device-to-host read, in front of the host-side sum).  ``t`` is not written."""
+    if sync_dist and dist.is_available() and dist.is_initialized():
+        t = (t.cpu() if dist.get_backend() == "gloo" else t).clone()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu()
 
 
 def trig_tables(cache: dict, lat_deg, lon_deg, device):

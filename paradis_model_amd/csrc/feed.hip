@@ -9,6 +9,7 @@
 // -ffp-contract=off.  HBM traffic: 4 B per output value (write only); the kernel is bound by the
 // 15 cosines per (time, cell).
 #include "common.h"
+#include "normalize.h"
 
 #pragma clang fp contract(off)
 
@@ -157,18 +158,17 @@ forcings_kernel(const double* __restrict__ lat_deg, const double* __restrict__ l
 // assemble_batch_kernel both call it, so a plane assembled by the second equals the first applied to a gathered copy.
 __device__ __forceinline__ float normalize_value(float x, int k, float a, float b, float eps_q, int inverse) {
   float r = x;
-  if (k == 1) {
-    r = inverse ? x * b + a : (x - a) / b;
-  } else if (k == 2) {
+  if (k == NORM_ZSCORE) {
+    r = inverse ? denorm_zscore(x, a, b) : (x - a) / b;
+  } else if (k == NORM_HUMIDITY) {
     const float lmin = logf(a), lmax = logf(b);
     if (!inverse) {
       r = (logf(fminf(fmaxf(x, 0.f), b) + eps_q) - lmin) / (lmax - lmin);
     } else {
-      const float q = expf(x * (lmax - lmin) + lmin) - eps_q;
-      r = fminf(fmaxf(q, 0.f), b);
+      r = denorm_humidity(x, lmin, lmax - lmin, b, eps_q);
     }
-  } else if (k == 3) {
-    r = inverse ? fmaxf(expf(x - 10.0f) - 1e-6f, 0.f) : logf(x + 1e-6f) + 10.0f;
+  } else if (k == NORM_PRECIP) {
+    r = inverse ? denorm_precip(x) : logf(x + NORM_PRECIP_EPS) + NORM_PRECIP_SHIFT;
   }
   return r;
 }
@@ -182,7 +182,7 @@ normalize_kernel(float* __restrict__ data, const int* __restrict__ kind, const f
   if (i >= n) return;
   const int c = (int)(i % C);
   const int k = kind[c];
-  if (k == 0) return;
+  if (k == NORM_NONE) return;
   data[i] = normalize_value(data[i], k, p0[c], p1[c], eps_q, inverse);
 }
 
@@ -192,10 +192,11 @@ normalize_kernel(float* __restrict__ data, const int* __restrict__ kind, const f
 // y = x.  log and exp are taken in double and rounded once: the correctly rounded float32 value, which every platform's
 // libm gives alike (logf / expf differ between libraries in the last bit, and a code would then depend on who packed).
 constexpr int PACK_MISSING = 65535;
+constexpr float PACK_LOG_EPS = 1e-6f;   // the store format's own shift of the log domain (not a normalisation constant)
 constexpr float PACK_TOP = 65534.0f;
 
 __device__ __forceinline__ float pack_domain_value(float x, int domain) {
-  return domain == 1 ? (float)log((double)(x + 1e-6f)) : x;
+  return domain == 1 ? (float)log((double)(x + PACK_LOG_EPS)) : x;
 }
 
 // the code of one packed-domain value; s == 0: a constant plane
@@ -210,7 +211,7 @@ __device__ __forceinline__ uint32_t pack_code(float y, float lo, float s) {
 __device__ __forceinline__ float unpack_value(uint32_t code, float lo, float s, int domain) {
   if (code == PACK_MISSING) return __builtin_nanf("");
   const float y = lo + s * (float)code;
-  return domain == 1 ? fmaxf((float)exp((double)y) - 1e-6f, 0.f) : y;
+  return domain == 1 ? fmaxf((float)exp((double)y) - PACK_LOG_EPS, 0.f) : y;
 }
 
 // The element readers of the plane copy below: where a plane of the store starts, and four / one of its values.

@@ -16,6 +16,7 @@
 // written back converted, plus the dew point), the 10 m wind triple, or a single remaining channel.
 // Algorithmic HBM bytes: 8*B*C*H*W (+ 4*B*L*H*W with the dew point).
 #include "common.h"
+#include "normalize.h"
 
 #pragma clang fp contract(off)
 
@@ -39,16 +40,14 @@ struct PostArgs {
   int n_units, B, H, W;
 };
 
-// fp32, the reference's order: x*std + mean; clip(exp(x*(log qmax - log qmin) + log qmin) - eps, 0, qmax);
-// max(exp(x - 10) - 1e-6, 0)
+// one value back to physical units by its channel's class (normalize.h); a, b: mean, std | q_min, q_max
 __device__ __forceinline__ float denorm(float x, int k, float a, float b, float eps_q) {
-  if (k == 1) return x * b + a;
-  if (k == 2) {
-    const float lmin = logf(a), lmax = logf(b);
-    const float q = expf(x * (lmax - lmin) + lmin) - eps_q;
-    return fminf(fmaxf(q, 0.f), b);
+  if (k == NORM_ZSCORE) return denorm_zscore(x, a, b);
+  if (k == NORM_HUMIDITY) {
+    const float lmin = logf(a);
+    return denorm_humidity(x, lmin, logf(b) - lmin, b, eps_q);
   }
-  if (k == 3) return fmaxf(expf(x - 10.0f) - 1e-6f, 0.f);
+  if (k == NORM_PRECIP) return denorm_precip(x);
   return x;
 }
 

@@ -19,14 +19,14 @@
 // stay fp32 (three ordinary stores per workgroup); the finishing kernel folds them in double.
 // Algorithmic HBM bytes: 8*B*C*H*W (the training loss kernel with its gradient store: 12).
 #include "common.h"
+#include "normalize.h"
 #include "stream_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int KIND_NONE = 2;
-constexpr int CLS_Z = 1, CLS_HUM = 2, CLS_PRECIP = 3;   // codes of paradis_normalize_features
+constexpr int KIND_NONE = 2;   // the loss kind "none"; the normalisation classes of the reports are normalize.h's NORM_*
 
 struct ScoreArgs {
   const float* pred;
@@ -53,13 +53,6 @@ __device__ __forceinline__ float loss_term(float e, int kind, float delta) {
   return (1.0f - s) * small + s * large;
 }
 
-// fp32, the reference's order: clip(exp(x (log qmax - log qmin) + log qmin) - 1e-12, 0, qmax); max(exp(x - 10) - 1e-6, 0)
-__device__ __forceinline__ float denorm_h(float x, float lmin, float lspan, float qmax) {
-  const float q = expf(x * lspan + lmin) - 1e-12f;
-  return fminf(fmaxf(q, 0.f), qmax);
-}
-__device__ __forceinline__ float denorm_p(float x) { return fmaxf(expf(x - 10.0f) - 1e-6f, 0.f); }
-
 template <bool VEC>
 __global__ void __launch_bounds__(256) val_score_kernel(ScoreArgs a) {
   const int c = blockIdx.x / a.nb;
@@ -72,9 +65,9 @@ __global__ void __launch_bounds__(256) val_score_kernel(ScoreArgs a) {
   if (with_loss || cls != 0) {       // (workgroup-uniform)
     const float* p = a.pred + (int64_t)b * a.pred_bs + (int64_t)c * a.P;
     const float* t = a.target + (int64_t)b * a.target_bs + (int64_t)c * a.P;
-    const float std_r = cls == CLS_Z ? a.rp1[c] : 1.0f;
+    const float std_r = cls == NORM_ZSCORE ? a.rp1[c] : 1.0f;
     float lmin = 0.f, lspan = 0.f, qmax = 0.f;
-    if (cls == CLS_HUM) {
+    if (cls == NORM_HUMIDITY) {
       qmax = a.rp1[c];
       lmin = logf(a.rp0[c]);
       lspan = logf(qmax) - lmin;
@@ -111,9 +104,10 @@ __global__ void __launch_bounds__(256) val_score_kernel(ScoreArgs a) {
         }
         if (cls != 0) {
           float d;
-          if (cls == CLS_Z) d = (tv[k] - pv[k]) * std_r;
-          else if (cls == CLS_HUM) d = denorm_h(tv[k], lmin, lspan, qmax) - denorm_h(pv[k], lmin, lspan, qmax);
-          else d = denorm_p(tv[k]) - denorm_p(pv[k]);
+          if (cls == NORM_ZSCORE) d = (tv[k] - pv[k]) * std_r;
+          else if (cls == NORM_HUMIDITY) d = denorm_humidity(tv[k], lmin, lspan, qmax, NORM_HUMIDITY_EPS) -
+                                            denorm_humidity(pv[k], lmin, lspan, qmax, NORM_HUMIDITY_EPS);
+          else d = denorm_precip(tv[k]) - denorm_precip(pv[k]);
           s2 += (d * d) * a.lat_w[hv[k]];
         }
       }
@@ -192,7 +186,7 @@ extern "C" int paradis_val_score(const float* pred, int64_t pred_bs, const float
   for (int r = 0; r < R; ++r) {
     PD_REQUIRE(rep_chan_host[r] >= 0 && rep_chan_host[r] < C, "val_score: report %d names channel %d of %d", r,
                rep_chan_host[r], C);
-    PD_REQUIRE(rep_class_host[r] >= CLS_Z && rep_class_host[r] <= CLS_PRECIP,
+    PD_REQUIRE(rep_class_host[r] >= NORM_ZSCORE && rep_class_host[r] <= NORM_PRECIP,
                "val_score: report %d has unknown normalisation class %d", r, rep_class_host[r]);
   }
   PD_REQUIRE(R == 0 || lat_w != nullptr, "val_score: reports need the latitude weight table");

@@ -19,7 +19,6 @@ bookkeeping only (names, counts, tables, lengths).
 """
 from __future__ import annotations
 
-import re
 from typing import Optional, Sequence
 
 import numpy as np
@@ -28,7 +27,7 @@ import torch
 from . import feed
 from ._lib import check, dptr, lib, require_hip, stream_ptr
 from .config import feature_layout
-from .feed import KIND_HUMIDITY, KIND_PRECIP, KIND_ZSCORE, times_to_us
+from .feed import KIND_HUMIDITY, KIND_PRECIP, times_to_us
 
 EPS_Q = 1e-12                       # era5_dataset.py:58
 SLAB_BYTES = 256 << 20              # host-to-device upload granularity of DeviceStore
@@ -37,11 +36,6 @@ PLANE_DTYPE = np.dtype([("feature", "<i4"), ("dt", "<i4"), ("kind", "<i4"), ("p0
 # the packed store (include/paradis_hip.h, "The 16-bit packed store"): per-feature domain of the packed quantity
 DOMAIN_LINEAR, DOMAIN_LOG = 0, 1
 PACK_MISSING = 65535
-
-
-def _base_name(feature: str) -> str:
-    """"temperature_h500" -> "temperature" (era5_dataset.py:469)"""
-    return re.sub(r"_h\d+$", "", feature)
 
 
 def pack_planes(slab: torch.Tensor, row0: int, codes: torch.Tensor, params: torch.Tensor, domain: torch.Tensor,
@@ -176,7 +170,7 @@ class DeviceStore:
         self.times_dev = self.times_us.to(self.device)
         self.packing = packing
         log_names = {str(n) for n in log_packed}
-        self.domain = np.array([DOMAIN_LOG if packing is not None and _base_name(f) in log_names else DOMAIN_LINEAR
+        self.domain = np.array([DOMAIN_LOG if packing is not None and feed.base_name(f) in log_names else DOMAIN_LINEAR
                                 for f in self.features], dtype=np.int32)
         rows = max(1, SLAB_BYTES // max(1, F * H * W * 4))
         if packing is None:
@@ -359,12 +353,7 @@ class DeviceDataset:
 
     # ------------------------------------------------------------------ tables
     def _kind_of(self, feature: str) -> int:
-        name = _base_name(feature)                      # era5_dataset.py:469-477
-        if self.custom_normalization and name == "total_precipitation_6hr":
-            return KIND_PRECIP
-        if self.custom_normalization and name == "specific_humidity":
-            return KIND_HUMIDITY
-        return KIND_ZSCORE
+        return feed.kind_of(feature, self.custom_normalization)
 
     def _tables(self, names, columns):
         st = self.store.stats

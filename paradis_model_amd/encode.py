@@ -31,7 +31,8 @@ import torch
 
 from . import _lib
 from ._lib import check, dptr, lib, require_hip, stream_ptr
-from ._tables import dense_state
+from ._tables import batch_stride, dense_state, device_tables
+from .feed import KIND_NONE
 
 # one row of paradis_encode_plane_t (include/paradis_hip.h)
 ENCODE_PLANE_DTYPE = np.dtype([("src", "<i4"), ("first", "<i4"), ("levels", "<i4"), ("level", "<i4")])
@@ -190,11 +191,7 @@ class EncodeSpec:
         return {"variables": variables, "total_pred_steps": total, "keepbits": self.keepbits, "dtype": "float32"}
 
     def device_table(self, device) -> torch.Tensor:
-        key = str(device)
-        if key not in self._dev:
-            with torch.inference_mode(False):
-                self._dev[key] = torch.from_numpy(self.table.view(np.uint8).copy()).to(device)
-        return self._dev[key]
+        return (self._dev.get(device) or device_tables(self._dev, device, device, (self.table.view(np.uint8),)))[0]
 
 
 def pred_slice(start_idx: int, n: int, with_init: bool = True) -> slice:
@@ -254,9 +251,9 @@ def encode_chunk(chunk: torch.Tensor, dew: Optional[torch.Tensor], spec: EncodeS
         raise ValueError(f"encode_chunk: out has {out.numel()} elements, {spec.numel(B, n_td, H, W)} are needed")
     P = H * W
 
-    def strides(t, state):          # (a stride of an axis of length 1 is arbitrary: the dense value stands in)
+    def strides(t, state):          # (batch, time): the time axis has its dense value too when it has one entry
         ts = t.stride(1) if n > 1 else state
-        return (t.stride(0) if B > 1 else n * ts), ts
+        return batch_stride(t, n * ts), ts
 
     cbs, cts = strides(chunk, C * P)
     dbs, dts = strides(dew, L * P) if dew is not None else (0, 0)
@@ -301,6 +298,6 @@ def initial_state(dataset, indices, post_spec, lat_deg, lon_deg):
         assemble_planes(store, idx, dataset.base, dataset.interval_steps, planes, 1, C, 0, 0, raw, None, dataset._flag)
         if missing:
             raw[:, missing] = float("nan")
-        spec0 = dataclasses.replace(post_spec, kind=np.zeros_like(post_spec.kind), _dev={})
+        spec0 = dataclasses.replace(post_spec, kind=np.full_like(post_spec.kind, KIND_NONE))
         postprocess(raw, spec0, lat_deg, lon_deg, state, 0, dew)
     return state, dew

@@ -8,6 +8,7 @@ No CPU fallback: the tensors must live on the HIP device.
 from __future__ import annotations
 
 import ctypes
+import re
 from typing import Sequence
 
 import numpy as np
@@ -18,7 +19,18 @@ from ._lib import check, dptr, lib, require_hip, stream_ptr
 FORCING_CODES = {"toa_incident_solar_radiation": 0, "sin_time_of_day": 1, "cos_time_of_day": 2,
                  "sin_year_progress": 3, "cos_year_progress": 4}
 DEFAULT_FORCINGS = tuple(FORCING_CODES)          # order of config/paradis_settings.yaml:214-219
-KIND_NONE, KIND_ZSCORE, KIND_HUMIDITY, KIND_PRECIP = 0, 1, 2, 3
+KIND_NONE, KIND_ZSCORE, KIND_HUMIDITY, KIND_PRECIP = 0, 1, 2, 3      # csrc/normalize.h
+
+
+def base_name(feature: str) -> str:
+    """"temperature_h500" -> "temperature" (reference data/era5_dataset.py:469)"""
+    return re.sub(r"_h\d+$", "", feature)
+
+
+def kind_of(feature: str, custom_normalization: bool) -> int:
+    """the normalisation class of a feature, by its base name (reference data/era5_dataset.py:469-477)"""
+    custom = {"total_precipitation_6hr": KIND_PRECIP, "specific_humidity": KIND_HUMIDITY} if custom_normalization else {}
+    return custom.get(base_name(feature), KIND_ZSCORE)
 
 
 def times_to_us(times) -> torch.Tensor:

@@ -15,17 +15,17 @@ No CPU fallback: the tensors must live on the HIP device.  fp32 only (the refere
 """
 from __future__ import annotations
 
-import re
 from dataclasses import dataclass, field
 from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib, harness
+from . import _lib, _tables
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import dense_state, trig_tables
-from .feed import KIND_HUMIDITY, KIND_PRECIP, KIND_ZSCORE
+from ._tables import batch_stride, dense_state, trig_tables
+from .feed import KIND_HUMIDITY, KIND_ZSCORE, base_name, kind_of
+from .rollout import ChunkRing, Stepper
 
 UNIT_SINGLE, UNIT_LEVEL, UNIT_SURFACE = 0, 1, 2
 _UNIT_INTS = 8
@@ -34,7 +34,7 @@ _UNIT_INTS = 8
 def var_indices(variable_name: str, variable_list: Sequence[str]) -> List[int]:
     """Positions of ``variable_name`` in a feature list with the ``_h<level>`` suffix stripped
     (reference utils/postprocessing.py:125-131)."""
-    return [i for i, var in enumerate(variable_list) if re.sub(r"_h\d+$", "", var) == variable_name]
+    return [i for i, var in enumerate(variable_list) if base_name(var) == variable_name]
 
 
 @dataclass
@@ -55,7 +55,7 @@ class PostSpec:
     winds: bool
     dewpoint: bool
     units: np.ndarray           # [U, 8] int32
-    _dev: dict = field(default_factory=dict, repr=False)
+    _dev: dict = field(default_factory=dict, init=False, repr=False)      # (init=False: a replace() starts empty)
     _trig: dict = field(default_factory=dict, repr=False)
 
     @property
@@ -86,15 +86,12 @@ class PostSpec:
         p1 = np.ones(C, np.float32)
         zs = []
         for i, f in enumerate(names):
-            base = re.sub(r"_h\d+$", "", f)
-            if base == "total_precipitation_6hr" and custom_normalization:
-                kind[i] = KIND_PRECIP
-            elif base == "specific_humidity" and custom_normalization:
+            kind[i] = kind_of(f, custom_normalization)
+            if kind[i] == KIND_HUMIDITY:
                 if q_min is None or q_max is None:
                     raise ValueError("custom_normalization with specific_humidity channels needs q_min and q_max")
-                kind[i], p0[i], p1[i] = KIND_HUMIDITY, float(q_min), float(q_max)
-            else:
-                kind[i] = KIND_ZSCORE
+                p0[i], p1[i] = float(q_min), float(q_max)
+            elif kind[i] == KIND_ZSCORE:
                 zs.append(i)
         mean = np.asarray(torch.as_tensor(zscore_mean).detach().cpu().numpy(), np.float32).reshape(-1)
         std = np.asarray(torch.as_tensor(zscore_std).detach().cpu().numpy(), np.float32).reshape(-1)
@@ -133,13 +130,8 @@ class PostSpec:
                    np.asarray(units, np.int32).reshape(-1, _UNIT_INTS))
 
     def device_tables(self, device):
-        key = str(device)
-        if key not in self._dev:
-            with torch.inference_mode(False):
-                self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (
-                    self.kind, self.p0, self.p1, self.units.reshape(-1),
-                    np.asarray(self.pressure_levels or [0.0], np.float64)))
-        return self._dev[key]
+        return self._dev.get(device) or _tables.device_tables(self._dev, device, device, (
+            self.kind, self.p0, self.p1, self.units.reshape(-1), np.asarray(self.pressure_levels or [0.0], np.float64)))
 
     def trig_tables(self, lat_deg, lon_deg, device):
         """the double sin / cos tables of the grid on ``device``, built once (``_tables.trig_tables``)"""
@@ -175,13 +167,10 @@ def postprocess(output: torch.Tensor, spec: PostSpec, lat_deg, lon_deg, chunk: t
     if (th, tw) != (H, W):
         raise ValueError(f"postprocess: lat/lon of {th} x {tw} points for a {H} x {W} state")
     kind, p0, p1, units, plev = spec.device_tables(output.device)
-
-    def bs(t, state):
-        return t.stride(0) if t.shape[0] > 1 else state
-
     work = 8.0 * B * C * P + (4.0 * B * L * P if dew is not None else 0.0)
-    _lib.call("forecast_post", work, dptr(output), bs(output, C * P), dptr(chunk), bs(chunk, T * C * P),
-              slot * chunk.stride(1), dptr(dew), bs(dew, T * L * P) if dew is not None else 0,
+    _lib.call("forecast_post", work, dptr(output), batch_stride(output, C * P), dptr(chunk),
+              batch_stride(chunk, T * C * P), slot * chunk.stride(1), dptr(dew),
+              batch_stride(dew, T * L * P) if dew is not None else 0,
               slot * dew.stride(1) if dew is not None else 0, dptr(kind), dptr(p0), dptr(p1), spec.eps_q,
               dptr(units), spec.units.shape[0], dptr(plev), L, dptr(trig), B, C, H, W, stream_ptr())
 
@@ -219,67 +208,35 @@ def chunk_plan(forecast_steps: int, output_frequency: int, write_every_n: Option
 
 
 # ---------------------------------------------------------------------------------- the predict loop
-class _GraphedStep:
-    """input assembly + model + feedback copy into the static input, captured once per (B, H, W)"""
-
-    def __init__(self, model, inp, forc, const, num_common, n_inputs):
-        with torch.inference_mode(False), torch.no_grad():
-            self.inp, self.forc, self.const = (torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
-                                               for t in (inp, forc, const))      # dense, whatever the views' strides
-
-            def step():
-                mi = harness.assemble_model_input(self.inp.unsqueeze(1), self.forc.unsqueeze(1), self.const.unsqueeze(1))
-                y = model(mi)
-                self.inp.copy_(harness.next_input(mi, y, num_common, n_inputs))
-                return y
-            self.graph, self.out = harness.capture_forward(step)
-
-    def load(self, inp, const):
-        self.inp.copy_(inp, non_blocking=True)
-        self.const.copy_(const, non_blocking=True)
-
-    def __call__(self, forc_step):
-        self.forc.copy_(forc_step, non_blocking=True)
-        self.graph.replay()
-        return self.out
-
-
 class Forecaster:
     """``LitParadis.predict_step`` (reference trainer.py:731-815) on the device.
 
     ``run(input_data [B,1,n_inputs*num_common,H,W], forcings [B,S,H,W,F], constants [B,1,H,W,K], on_chunk)`` rolls the
-    model out for S steps under ``torch.no_grad()``; every ``output_frequency``-th output goes through ``postprocess``
-    into the current chunk on the device; a finished chunk is copied by a side stream into one of two pinned host
-    buffers and ``on_chunk(forecast=<numpy [B,n,C,H,W]>, start_idx=<int>, dewpoint=<numpy [B,n,L,H,W] or None>)`` is
-    called - the arguments of the reference's ``write_forecast_chunk``.  The arrays are views of the pinned buffers,
-    valid until ``on_chunk`` returns.  A chunk is handed over when the next one has been enqueued (or at the end), so
-    the rollout does not wait for the copy or for the writer.  ``on_chunk=None``: the chunks are computed and copied but
-    not handed over, and ``run`` returns without waiting for the device (warm-up, timing).
-
-    ``graph=True``: the forward step is captured into a HIP graph per (B, H, W) after an eager warm-up, outside
-    ``ops.frozen_weights()`` - the weight-image kernels are nodes of the graph, so parameters written in place between
-    runs (``load_state_dict``, an optimiser step) are honoured by the next replay.  Per step the host then issues one
-    forcing copy, one replay and (stored steps) one post-processing launch.
+    model out for S steps under ``torch.no_grad()`` (``rollout.Stepper``; ``graph=True``: a step is one forcing copy and
+    one HIP-graph replay that honours parameters written in place between runs); every ``output_frequency``-th output
+    goes through ``postprocess`` into the current chunk on the device; a finished chunk is copied by a side stream into
+    pinned host memory (``rollout.ChunkRing``) and ``on_chunk(forecast=<numpy [B,n,C,H,W]>, start_idx=<int>,
+    dewpoint=<numpy [B,n,L,H,W] or None>)`` is called - the arguments of the reference's ``write_forecast_chunk``.  The
+    arrays are views of the pinned tensors, valid until ``on_chunk`` returns.  A chunk is handed over when the next one
+    has been enqueued (or at the end), so the rollout does not wait for the copy or for the writer.  ``on_chunk=None``:
+    the chunks are computed and copied but not handed over, and ``run`` returns without waiting for the device.
 
     ``run(..., scorecard=<verify.Scorecard>, truth=<[B, n_stored, C, H, W] on the device>, truth_normalized=False,
     clim_index=<int32 [B, n_stored] or None>)``: right after the post-processing of stored state ``k`` the finished state
     is scored in place against ``truth[:, k]`` at lead ``k`` (``scorecard.update``, one launch pair on the main stream, in
     front of the event the side-stream copy waits for).  ``truth_normalized=True``: the truth is in model space (a
-    validation batch's ``true_data``) and goes through the same ``postprocess`` into a scratch state first.  Without a
-    scorecard ``run`` issues exactly the launches it issued before; a scorecard without ``truth``, or a truth of another
-    ``n_stored``, is refused before the rollout starts.
+    validation batch's ``true_data``) and goes through the same ``postprocess`` into a scratch state first.  A scorecard
+    without ``truth``, or a truth of another ``n_stored``, is refused before the rollout starts.
 
     ``run(..., encoder=<encode.EncodeSpec>, init=<(state [B, 1, C, H, W], dew [B, 1, L, H, W] or None) or None>)``: a
     flushed chunk is regrouped into the writer's named variables and BitRounded on the device (``encode.encode_chunk``,
-    one launch on the main stream in front of the event the side-stream copy waits for) into one of two encoded device
-    buffers; the side stream copies that buffer - not the plain chunk - into one of two pinned buffers of the same layout
-    and ``on_chunk(variables=<dict name -> numpy view [B, n_td, (L,) H, W]>, start_idx=<int>, pred_slice=<slice>)`` is
-    called with the hand-over timing described above.  With ``init`` (``encode.initial_state``) the first chunk carries
-    that state in slot 0 (``n_td = n + 1``, ``pred_slice = slice(0, 1 + n)``, as the reference's writer); without it,
-    and for every later chunk, ``n_td = n`` and ``pred_slice = slice(1 + start_idx, 1 + start_idx + n)``.  A scorecard
-    keeps scoring the un-encoded state.  Refused before the rollout starts: an encoder whose names are not
-    ``PostSpec.names``, one with ``dewpoint=True`` on a forecaster without the dew point, an ``init`` of another shape.
-    Without ``encoder`` ``run`` issues exactly the launches it issued before."""
+    one launch on the main stream) into a ring of its own, which is handed over in place of the plain chunk, with the
+    same timing: ``on_chunk(variables=<dict name -> numpy view [B, n_td, (L,) H, W]>, start_idx=<int>,
+    pred_slice=<slice>)``.  With ``init`` (``encode.initial_state``) the first chunk carries that state in slot 0
+    (``n_td = n + 1``, ``pred_slice = slice(0, 1 + n)``, as the reference's writer); without it, and for every later
+    chunk, ``n_td = n`` and ``pred_slice = slice(1 + start_idx, 1 + start_idx + n)``.  A scorecard keeps scoring the
+    un-encoded state.  Refused before the rollout starts: an encoder whose names are not ``PostSpec.names``, one with
+    ``dewpoint=True`` on a forecaster without the dew point, an ``init`` of another shape."""
 
     def __init__(self, model, spec: PostSpec, lat_deg, lon_deg, *, num_common: int = 83, n_inputs: int = 2,
                  output_frequency: int = 1, write_every_n: Optional[int] = None, graph: bool = True,
@@ -291,30 +248,17 @@ class Forecaster:
         self.output_frequency, self.write_every_n = int(output_frequency), write_every_n
         self.graph = bool(graph)
         self.dewpoint = spec.dewpoint if dewpoint is None else bool(dewpoint)
-        self._steps = {}       # (B, H, W) -> _GraphedStep
-        self._bufs = {}        # chunk shape -> device chunks, pinned buffers, events
+        self._stepper = Stepper(model, self.num_common, self.n_inputs, self.graph)
+        self._steps = self._stepper.steps      # (B, H, W) -> rollout.GraphedStep
+        self._rings = {}       # (device, pair shapes) -> rollout.ChunkRing
         self._truth = {}       # (B, C, H, W, device) -> [B, 1, C, H, W]: a model-space truth state in physical units
-        self._enc = {}         # chunk shape -> two encoded device buffers, two pinned buffers of the same layout
 
-    def _buffers(self, B, n, C, L, H, W, device, pinned=True):
-        """device chunks, pinned buffers, events; ``pinned=False`` (the encoded hand-over, which has pinned buffers of its
-        own layout) leaves the plain pinned buffers unallocated until a run needs them"""
-        key = (B, n, C, L, H, W, str(device), self.dewpoint)
-        with torch.inference_mode(False):
-            if key not in self._bufs:
-                dev = [torch.empty(B, n, C, H, W, device=device) for _ in range(2)]
-                ddev = [None, None]
-                if self.dewpoint:
-                    ddev = [torch.empty(B, n, L, H, W, device=device) for _ in range(2)]
-                self._bufs[key] = (dev, [None, None], ddev, [None, None], [torch.cuda.Event() for _ in range(2)],
-                                   [torch.cuda.Event() for _ in range(2)], torch.cuda.Stream(device=device),
-                                   [False, False])
-            host, dhost = self._bufs[key][1], self._bufs[key][3]
-            if pinned and host[0] is None:
-                host[:] = [torch.empty(B, n, C, H, W, pin_memory=True) for _ in range(2)]
-                if self.dewpoint:
-                    dhost[:] = [torch.empty(B, n, L, H, W, pin_memory=True) for _ in range(2)]
-        return self._bufs[key]
+    def _ring(self, device, shapes, pinned=True) -> ChunkRing:
+        """the ring of these pairs, kept per shape; ``pinned=False``: no pinned tensors until a run hands this ring over"""
+        key = (str(device), tuple(shapes.items()))
+        ring = self._rings.get(key) or self._rings.setdefault(key, ChunkRing(device, shapes))
+        ring.pending.clear()           # (a run that ended in an exception may have left some)
+        return ring.pin() if pinned else ring
 
     def _check_verification(self, scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W):
         """the refusals of ``run(scorecard=...)``, before the rollout starts; returns the forecaster's ``[B, 1, C, H, W]``
@@ -366,15 +310,6 @@ class Forecaster:
             raise ValueError(f"Forecaster.run: init must be ({(B, 1, C, H, W)}, {(B, 1, L, H, W)} or None)")
         return state, dew
 
-    def _encoded_buffers(self, B, n, H, W, numel, device):
-        """per chunk shape, like ``_buffers``: its events order the accesses to these too"""
-        key = (B, n, H, W, numel, str(device))
-        if key not in self._enc:
-            with torch.inference_mode(False):
-                self._enc[key] = ([torch.empty(numel, device=device) for _ in range(2)],
-                                  [torch.empty(numel, pin_memory=True) for _ in range(2)])
-        return self._enc[key]
-
     @torch.no_grad()
     def run(self, input_data, forcings, constants, on_chunk: Optional[Callable],
             forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
@@ -391,97 +326,49 @@ class Forecaster:
         C, L = self.spec.num_channels, self.spec.num_levels
         truth_phys = self._check_verification(scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W)
         init = self._check_encoder(encoder, init, B, C, L, H, W)
-        n_chunk = min(n_stored, S if self.write_every_n is None else int(self.write_every_n))
-        dev, host, ddev, dhost, filled, copied, side, used = self._buffers(B, n_chunk, C, L, H, W, input_data.device,
-                                                                            pinned=encoder is None)
+        sizes = [p.flush[1] for p in plan if p.flush is not None]         # per chunk its number of states
+        n_chunk, sizes = max(sizes), iter(sizes)
+        shapes = {"state": (B, n_chunk, C, H, W), **({"dew": (B, n_chunk, L, H, W)} if self.dewpoint else {})}
+        ring = chunks = self._ring(input_data.device, shapes, pinned=encoder is None)   # (written, handed over)
         if encoder is not None:
             from .encode import encode_chunk, pred_slice
-            enc, henc = self._encoded_buffers(B, n_chunk, H, W, encoder.numel(B, n_chunk + 1, H, W), input_data.device)
-        main = torch.cuda.current_stream()
-        const = constants[:, :1].permute(0, 1, 4, 2, 3)
-        forc = forcings.permute(0, 1, 4, 2, 3)
-        step_fn = None
-        if self.graph:
-            key = (B, H, W)
-            if key not in self._steps:
-                from . import ops
-                with ops.frozen_weights(False):
-                    self._steps[key] = _GraphedStep(self.model, input_data[:, 0], forc[:, 0], const[:, 0],
-                                                    self.num_common, self.n_inputs)
-            step_fn = self._steps[key]
-            step_fn.load(input_data[:, 0], const[:, 0])
-        cur = input_data
-        # per chunk its number of states, known in advance: a trailing partial chunk uses a dense [B, n, ...] view of the
-        # same storage, so every device-to-host copy is one contiguous transfer
-        sizes = [p.flush[1] for p in plan if p.flush is not None]
+            # (axis 1 is not time: numel is linear in n_td, so a chunk's blocks [B, n_td, L_v, H, W] are a dense prefix)
+            ring = self._ring(input_data.device, {"encoded": (1, n_chunk + 1, encoder.numel(B, 1, H, W))})
 
-        def views(j, n):
-            def v(t, ch):
-                return None if t is None else t.view(-1)[:B * n * ch * H * W].view(B, n, ch, H, W)
-            return v(dev[j], C), v(host[j], C), v(ddev[j], L), v(dhost[j], L)
-
-        def slots(start, n):         # (n_td, td_off) of a chunk's encoded blocks: the first one carries the init state
-            return (n + 1, 1) if (start == 0 and init is not None) else (n, 0)
-
-        def deliver(p):
-            if on_chunk is None:
-                return
-            j, start, n = p
-            copied[j].synchronize()
-            if encoder is not None:
-                n_td, _ = slots(start, n)
-                on_chunk(variables=encoder.views(henc[j].numpy(), B, n_td, H, W), start_idx=start,
+        def hand_over(start, n, host):             # (rollout.ChunkRing: rule 4)
+            if encoder is None:
+                on_chunk(forecast=host["state"].numpy(), start_idx=start,
+                         dewpoint=host["dew"].numpy() if self.dewpoint else None)
+            else:
+                e = host["encoded"]
+                on_chunk(variables=encoder.views(e.numpy(), B, e.shape[1], H, W), start_idx=start,
                          pred_slice=pred_slice(start, n, with_init=init is not None))
-                return
-            _, h, _, dh = views(j, n)
-            on_chunk(forecast=h.numpy(), start_idx=start, dewpoint=dh.numpy() if self.dewpoint else None)
 
-        pending = None         # (buffer index, start_idx, n) enqueued for copy, not yet handed over
-        i_chunk = 0
+        self._stepper.begin(input_data, forcings, constants)
         i_stored = 0
         for step, p in enumerate(plan):
-            if step_fn is not None:
-                out = step_fn(forc[:, step])
-            else:
-                mi = harness.assemble_model_input(cur, forc[:, step].unsqueeze(1), const)
-                out = self.model(mi)
-                cur = harness.next_input(mi, out, self.num_common, self.n_inputs).unsqueeze(1)
-            k = i_chunk & 1
+            out = self._stepper.step(step)
             if p.stored:
                 if p.slot == 0:
-                    d, h, dd, dh = views(k, sizes[i_chunk])
-                    if used[k]:
-                        main.wait_event(copied[k])     # the side stream has finished reading this device chunk
+                    views = chunks.open(next(sizes))
+                    d, dd = views["state"], views.get("dew")
                 postprocess(out, self.spec, self.lat_deg, self.lon_deg, d, p.slot, dd)
-                if scorecard is not None:      # on the main stream, in front of `filled`: the copy sees a finished chunk
+                if scorecard is not None:
                     t = truth[:, i_stored]
-                    if truth_phys is not None:
+                    if truth_phys is not None:             # a model-space truth: to physical units first
                         postprocess(t, self.spec, self.lat_deg, self.lon_deg, truth_phys, 0)
                         t = truth_phys[:, 0]
                     scorecard.update(i_stored, d[:, p.slot], t, None if clim_index is None else clim_index[:, i_stored])
                 i_stored += 1
             if p.flush is not None:
                 start, n = p.flush
-                if encoder is not None:        # on the main stream, in front of `filled`, into the buffer `copied[k]` guards
-                    n_td, td_off = slots(start, n)
+                if encoder is not None:
+                    n_td, td_off = (n + 1, 1) if (start == 0 and init is not None) else (n, 0)   # the init state's slot
+                    enc = ring.open(n_td)["encoded"]
                     if td_off:
-                        encode_chunk(init[0], init[1], encoder, enc[k], n_td, 0)
-                    encode_chunk(d, dd if encoder.dewpoint else None, encoder, enc[k], n_td, td_off)
-                    m = encoder.numel(B, n_td, H, W)
-                filled[k].record(main)
-                with torch.cuda.stream(side):
-                    side.wait_event(filled[k])
-                    if encoder is not None:
-                        henc[k][:m].copy_(enc[k][:m], non_blocking=True)
-                    else:
-                        h.copy_(d, non_blocking=True)
-                        if self.dewpoint:
-                            dh.copy_(dd, non_blocking=True)
-                    copied[k].record(side)
-                used[k] = True
-                if pending is not None:
-                    deliver(pending)               # chunk i-1; its pinned buffer is the one chunk i+1 will be copied into
-                pending = (k, start, n)
-                i_chunk += 1
-        if pending is not None:
-            deliver(pending)
+                        encode_chunk(init[0], init[1], encoder, enc, n_td, 0)
+                    encode_chunk(d, dd if encoder.dewpoint else None, encoder, enc, n_td, td_off)
+                ring.flush(p.flush)
+                ring.deliver(on_chunk and hand_over)       # chunk i-1: chunk i+1 will be copied into its pinned tensors
+        ring.deliver(on_chunk and hand_over, keep=0)
+        self._stepper.end()

@@ -19,7 +19,7 @@ import torch
 
 from . import feed
 from ._lib import check, dptr, lib, require_hip, stream_ptr
-from ._tables import trig_tables, workspace
+from ._tables import device_tables, trig_tables, workspace
 
 # one row of paradis_wind_row_t (include/paradis_hip.h)
 WIND_DTYPE = np.dtype([("src_u", "<i4"), ("src_v", "<i4"), ("src_w", "<i4"), ("src_t", "<i4"), ("dst_x", "<i4"),
@@ -65,14 +65,10 @@ class WindPlan:
         # src may be dst when no destination column is a column that some row reads
         read = {int(r[k]) for r in rows for k in ("src_u", "src_v", "src_w", "src_t")} - {-1}
         self.in_place_ok = not (read & set(written))
-        self._dev = {}
-        self._trig = {}
+        self._dev, self._trig = {}, {}
 
     def device_rows(self, device) -> torch.Tensor:
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = torch.from_numpy(self.rows.view(np.uint8).copy()).to(device)
-        return self._dev[key]
+        return (self._dev.get(device) or device_tables(self._dev, device, device, (self.rows.view(np.uint8),)))[0]
 
     def trig_tables(self, lat_deg, lon_deg, device):
         """the double sin / cos tables of the grid on ``device``, built once (``_tables.trig_tables``)"""

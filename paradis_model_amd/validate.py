@@ -7,8 +7,7 @@ latitude-weighted RMSE in physical units of the configured report features (``_g
 The reference evaluates these with a dozen full-size ATen passes per step and reads every logged value on the host.
 Here one HIP launch pair (``csrc/score.hip``) reads the model output and the target view once and leaves all numbers of
 the step in one row on the device; rows are accumulated on the device and read once, in ``Validator.result``.  With
-``graph=True`` the forward step (input assembly, model, feedback copy) is one HIP-graph replay
-(``forecast._GraphedStep``).
+``graph=True`` the forward step (input assembly, model, feedback copy) is one HIP-graph replay (``rollout.Stepper``).
 
 No CPU fallback: the tensors must live on the HIP device.
 """
@@ -21,11 +20,11 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, harness
+from . import _lib, _tables
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import dense_state, workspace
+from ._tables import batch_stride, dense_state, sum_over_ranks, workspace
 from .feed import KIND_HUMIDITY, KIND_PRECIP, KIND_ZSCORE
-from .forecast import _GraphedStep
+from .rollout import Stepper
 
 LOSS_KIND = {"mse": 0, "reversed_huber": 1, "amse": 2}       # 2 = none: the AMSE value comes from ops.amse_loss
 
@@ -68,6 +67,7 @@ class ReportSpec:
             if f not in feature_names:
                 raise ValueError(f"report feature '{f}' is not among the feature names")
             chan[r] = feature_names.index(f)
+            # (substring tests: the reference's own rule for reports, trainer.py:277-283 - not feed.kind_of's base names)
             if custom_normalization and "specific_humidity" in f:
                 if q_min is None or q_max is None:
                     raise ValueError("custom_normalization with a specific_humidity report needs q_min and q_max")
@@ -85,7 +85,7 @@ class ReportSpec:
 
     def device_tables(self, device, C: int):
         """(rflag [C], rcls [C], rp0 [C], rp1 [C], rchan [R]) on ``device``"""
-        key = (str(device), int(C))
+        key = (device, int(C))
         if key not in self._dev:
             if self.num_reports and int(self.chan.max()) >= C:
                 raise ValueError(f"report channel {int(self.chan.max())} outside a {C}-channel state")
@@ -95,9 +95,7 @@ class ReportSpec:
                 c = int(self.chan[r])
                 rflag[c], rcls[c], rp0[c], rp1[c] = r, self.cls[r], self.p0[r], self.p1[r]
             rchan = self.chan if self.num_reports else np.zeros(1, np.int32)
-            with torch.inference_mode(False):
-                self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device)
-                                       for a in (rflag, rcls, rp0, rp1, rchan))
+            _tables.device_tables(self._dev, key, device, (rflag, rcls, rp0, rp1, rchan))
         return self._dev[key]
 
 
@@ -137,15 +135,12 @@ def score(pred: torch.Tensor, target: torch.Tensor, loss, reports: Optional[Repo
                          f"{C} x {H} x {W} state")
     wl = lat if loss.apply_latitude_weights else None
     P = H * W
-
-    def bs(t):
-        return t.stride(0) if B > 1 else C * P
-
     tabs = reports.device_tables(pred.device, C) if R else (None,) * 5
     chan_h = reports.chan.ctypes.data_as(ctypes.c_void_p) if R else None
     cls_h = reports.cls.ctypes.data_as(ctypes.c_void_p) if R else None
     ws = workspace(_WS, pred.device, int(_lib.lib.paradis_val_score_ws_bytes(B, C, H, W)))
-    _lib.call("val_score", 8.0 * B * C * P, dptr(pred), bs(pred), dptr(target), bs(target), dptr(wf), dptr(wl),
+    _lib.call("val_score", 8.0 * B * C * P, dptr(pred), batch_stride(pred, C * P), dptr(target),
+              batch_stride(target, C * P), dptr(wf), dptr(wl),
               dptr(lat) if R else None, LOSS_KIND[loss.kind], float(loss.delta), chan_h, cls_h, R,
               *(dptr(t) for t in tabs), dptr(out_row), dptr(ws), B, C, H, W, stream_ptr())
 
@@ -165,11 +160,11 @@ class Validator:
     initialised process group the accumulator vector and its weight are summed over the ranks by ONE all-reduce first
     (the reference: one per logged value).  ``reset()`` clears the accumulators.
 
-    ``graph=True``: forward and feedback copy are one HIP-graph replay per step, captured per (B, H, W) outside
-    ``ops.frozen_weights()``, so an optimiser step between two validations is honoured; scoring runs outside the
-    graph.  ``amp=True``: the forward runs under ``torch.autocast(bfloat16)``; the output is scored in fp32.
-    An ``"amse"`` validation loss: row entry 0 is ``val_loss(out, target)`` (``ops.amse_loss``), the per-channel
-    entries are zeros.  ``keep_outputs=True`` keeps clones of the last ``step``'s outputs in ``self.outputs``."""
+    ``graph=True``: forward and feedback copy are one HIP-graph replay per step that honours an optimiser step between
+    two validations (``rollout.Stepper``); scoring runs outside the graph.  ``amp=True``: the forward runs under
+    ``torch.autocast(bfloat16)``; the output is scored in fp32.  An ``"amse"`` validation loss: row entry 0 is
+    ``val_loss(out, target)`` (``ops.amse_loss``), the per-channel entries are zeros.  ``keep_outputs=True`` keeps
+    clones of the last ``step``'s outputs in ``self.outputs``."""
 
     def __init__(self, model, val_loss, reports: Optional[ReportSpec] = None, *, num_common: int = 83,
                  n_inputs: int = 2, graph: bool = True, amp: bool = False, keep_outputs: bool = False):
@@ -178,7 +173,8 @@ class Validator:
         self.graph, self.amp, self.keep_outputs = bool(graph), bool(amp), bool(keep_outputs)
         self.channel_names = list(val_loss.output_name_order)
         self.outputs: List[torch.Tensor] = []
-        self._steps = {}       # (B, H, W) -> _GraphedStep
+        self._stepper = Stepper(self._forward, self.num_common, self.n_inputs, self.graph)
+        self._steps = self._stepper.steps      # (B, H, W) -> rollout.GraphedStep
         self._acc = None       # float64 [1 + 2C + R] on the device: sum over batches of B * (mean over steps)
         self._weight = 0       # sum of B (host: the batch size is known without the device)
 
@@ -196,39 +192,23 @@ class Validator:
             raise ValueError(f"{S} target steps need as many forcing steps, got {forcings.shape[1]}")
         R = self.reports.num_reports if self.reports is not None else 0
         n = row_size(C, R)
-        const = constant_data[:, :1].permute(0, 1, 4, 2, 3)
-        forc = forcings.permute(0, 1, 4, 2, 3)
         with torch.inference_mode(False):
             rows = torch.empty(S, n, device=true_data.device)
             if self._acc is None or self._acc.numel() != n or self._acc.device != true_data.device:
                 self._acc, self._weight = torch.zeros(n, dtype=torch.float64, device=true_data.device), 0
-        step_fn = None
-        if self.graph:
-            key = (B, H, W)
-            if key not in self._steps:
-                from . import ops
-                with ops.frozen_weights(False):
-                    self._steps[key] = _GraphedStep(self._forward, input_data[:, 0], forc[:, 0], const[:, 0],
-                                                    self.num_common, self.n_inputs)
-            step_fn = self._steps[key]
-            step_fn.load(input_data[:, 0], const[:, 0])
-        cur = input_data
+        self._stepper.begin(input_data, forcings, constant_data)
         amse = self.val_loss.kind == "amse"
         if self.keep_outputs:
             self.outputs = []
         for s in range(S):
-            if step_fn is not None:
-                out = step_fn(forc[:, s])
-            else:
-                mi = harness.assemble_model_input(cur, forc[:, s].unsqueeze(1), const)
-                out = self._forward(mi)
-                cur = harness.next_input(mi, out, self.num_common, self.n_inputs).unsqueeze(1)
+            out = self._stepper.step(s)
             target = true_data[:, s]
             score(out, target, self.val_loss, self.reports, rows[s])
             if amse:
                 rows[s, :1].copy_(self.val_loss(out, target).reshape(1))
             if self.keep_outputs:
                 self.outputs.append(out.clone())
+        self._stepper.end()
         self._acc.add_(rows.sum(dim=0, dtype=torch.float64), alpha=float(B) / S)
         self._weight += B
         return rows
@@ -241,18 +221,12 @@ class Validator:
     def result(self, sync_dist: bool = False) -> Dict[str, float]:
         if self._acc is None or self._weight == 0:
             raise RuntimeError("Validator.result: no batch has been scored since the last reset")
-        import torch.distributed as dist
         n = self._acc.numel()
-        if sync_dist and dist.is_available() and dist.is_initialized():
-            vec = torch.cat([self._acc, self._acc.new_tensor([float(self._weight)])])
-            if dist.get_backend() == "gloo":
-                vec = vec.cpu()              # the one device-to-host read, in front of the host-side sum
-            dist.all_reduce(vec, op=dist.ReduceOp.SUM)
-            vec = vec.cpu()
+        acc, weight = self._acc, float(self._weight)
+        if sync_dist:          # the accumulators and their weight travel as one vector
+            vec = sum_over_ranks(torch.cat([acc, acc.new_tensor([weight])]), True)
             acc, weight = vec[:n], float(vec[n])
-        else:
-            acc, weight = self._acc.cpu(), float(self._weight)
-        v = (acc / weight).tolist()
+        v = (acc.cpu() / weight).tolist()
         C = len(self.channel_names)
         res = {"val_loss": v[0]}
         if self.reports is not None:

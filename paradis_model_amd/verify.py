@@ -33,7 +33,7 @@ import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import dense_state, workspace
+from ._tables import batch_stride, dense_state, sum_over_ranks, workspace
 
 ACC_FIELDS = 8          # {n, sum se, sum e, sum ae, sum acc_b, n_acc, sum ff, sum tt}
 METRICS = ("rmse", "bias", "mae", "acc", "activity")
@@ -146,14 +146,11 @@ class Scorecard:
                 raise ValueError("Scorecard.update: clim_index must live on the device")
             clim_index = clim_index.contiguous()         # a column of [B, n_stored] becomes dense; no host wait
         P = H * W
-
-        def bs(t):
-            return t.stride(0) if B > 1 else C * P
-
         with_clim = clim is not None
         ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_verify_ws_bytes(B, C, H, W, int(with_clim))))
-        _lib.call("verify_update", (12.0 if with_clim else 8.0) * B * C * P, dptr(forecast), bs(forecast), dptr(truth),
-                  bs(truth), dptr(clim), dptr(clim_index) if with_clim else None, clim.shape[0] if with_clim else 0,
+        _lib.call("verify_update", (12.0 if with_clim else 8.0) * B * C * P, dptr(forecast),
+                  batch_stride(forecast, C * P), dptr(truth), batch_stride(truth, C * P), dptr(clim),
+                  dptr(clim_index) if with_clim else None, clim.shape[0] if with_clim else 0,
                   dptr(self.lat_w), float(W) * self._wsum, dptr(self.acc[int(lead)]), dptr(ws), B, C, H, W,
                   stream_ptr())
 
@@ -161,14 +158,7 @@ class Scorecard:
         self.acc.zero_()
 
     def result(self, sync_dist: bool = False) -> dict:
-        import torch.distributed as dist
-        acc = self.acc
-        if sync_dist and dist.is_available() and dist.is_initialized():
-            acc = acc.clone()
-            if dist.get_backend() == "gloo":
-                acc = acc.cpu()                  # the one device-to-host read, in front of the host-side sum
-            dist.all_reduce(acc, op=dist.ReduceOp.SUM)
-        a = acc.cpu().numpy()
+        a = sum_over_ranks(self.acc, sync_dist).numpy()
         n, n_acc = a[..., 0], a[..., 5]
         with np.errstate(divide="ignore", invalid="ignore"):
             res = {"rmse": np.sqrt(a[..., 1] / n), "bias": a[..., 2] / n, "mae": a[..., 3] / n}

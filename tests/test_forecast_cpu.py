@@ -144,3 +144,26 @@ def test_forecast_entry_point_is_exported_and_refuses_cpu_tensors():
     lat, lon = FO.grid_deg(8, 16, False)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         postprocess(torch.zeros(1, 97, 8, 16), spec, lat, lon, torch.zeros(1, 1, 97, 8, 16), 0)
+
+
+@pytest.mark.parametrize("custom", [True, False])
+def test_kind_of_is_one_rule(custom):
+    """the normalisation class of a feature is ``feed.kind_of``, for the post-processing tables and the dataset alike"""
+    from types import SimpleNamespace
+    from paradis_model_amd import feed
+    from paradis_model_amd.config import default_config, feature_layout
+    from paradis_model_amd.dataset import DeviceDataset
+    from paradis_model_amd.forecast import PostSpec
+    cfg = default_config()
+    names = list(feature_layout(cfg).output_name_order)
+    want = [feed.kind_of(f, custom) for f in names]
+    assert set(want) == ({feed.KIND_ZSCORE, feed.KIND_HUMIDITY, feed.KIND_PRECIP} if custom else {feed.KIND_ZSCORE})
+    n_z = want.count(feed.KIND_ZSCORE)
+    spec = PostSpec.from_features(names, list(cfg.features.pressure_levels), zscore_mean=torch.zeros(n_z),
+                                  zscore_std=torch.ones(n_z), q_min=FO.Q_MIN, q_max=FO.Q_MAX,
+                                  custom_normalization=custom)
+    assert spec.kind.tolist() == want
+    stub = SimpleNamespace(custom_normalization=custom)              # no store: the method reads this attribute only
+    assert [DeviceDataset._kind_of(stub, f) for f in names] == want
+    assert feed.base_name("temperature_h500") == "temperature"
+    assert feed.base_name("2m_temperature") == "2m_temperature" and feed.base_name("wind_x_10m") == "wind_x_10m"

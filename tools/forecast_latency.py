@@ -121,6 +121,39 @@ def rollout_times(B, steps, rounds):
             "eager_ms_all": [round(v, 3) for v in ms[False]], "graph_ms_all": [round(v, 3) for v in ms[True]]}
 
 
+def host_times(steps, rounds=7):
+    """host time per step of the graphed run with on_chunk=None (nothing synchronised inside the timed call), B = 1,
+    every step stored, chunks of 2 - the most hand-over work per step - plain and with an encoder"""
+    from paradis_model_amd.config import default_config, stub_datamodule
+    from paradis_model_amd.encode import EncodeSpec
+    from paradis_model_amd.forecast import Forecaster
+    from paradis_model_amd.harness import make_grids, synthetic_batch
+    from paradis_model_amd.model import Paradis
+    cfg = default_config()
+    H, W = 32, 64
+    _, lg, og = make_grids(H, W, False)
+    torch.manual_seed(42)
+    model = Paradis(stub_datamodule(cfg), cfg, lg, og).cuda().eval()
+    inp, _, forc, const = synthetic_batch(H, W, False, 1, steps, device="cuda")
+    lat, lon = grid_deg(H, W, False)
+    spec = make_spec()
+    enc = EncodeSpec.from_config(cfg, spec.names, list(cfg.features.pressure_levels))
+    res = {"grid": f"{H}x{W}", "B": 1, "steps": steps, "write_every_n": 2, "rounds": rounds}
+    for name, kw in (("plain", {}), ("encoded", {"encoder": enc})):
+        fc = Forecaster(model, spec, lat, lon, write_every_n=2, graph=True)
+        fc.run(inp, forc, const, lambda **k: None, **kw)
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(rounds):
+            t0 = time.perf_counter()
+            fc.run(inp, forc, const, None, **kw)
+            ms.append(1e3 * (time.perf_counter() - t0) / steps)
+            torch.cuda.synchronize()
+        res[f"{name}_host_ms_per_step"] = round(statistics.median(ms), 4)
+        res[f"{name}_host_ms_all"] = [round(v, 4) for v in ms]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -131,7 +164,7 @@ def main():
         raise SystemExit("forecast_latency.py needs the GPU")
     from paradis_model_amd import ops
     res = {"tool": "forecast_latency", "device": torch.cuda.get_device_name(0), "gemm": ops.gemm_scheme_name(),
-           "rollout": [], "post": []}
+           "rollout": [], "post": [], "host": host_times(max(40, a.steps))}
     for B in (1, 4):
         res["post"].append(post_times(B, 32, 64, False))
         res["rollout"].append(rollout_times(B, max(40, a.steps), a.rounds))
