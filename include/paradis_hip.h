@@ -668,6 +668,42 @@ int paradis_cartesian_winds(const float* src, int Fs, float* dst, int Fd, const 
                             const paradis_wind_row_t* rows_host, int n_rows, const double* trig, int T, int H, int W,
                             void* stream);
 
+/* ---- The verification climatology of a device-resident store (ABI 10, additive), csrc/climatology.hip: the slot means
+ * that paradis_verify_update reads as clim [K, C, H, W].  The project's own windowed day-of-year x hour definition
+ * (climatology.ClimPlan builds the lists on the host); not pinned against WeatherBench-2.
+ *
+ * paradis_clim_mean / paradis_clim_mean_packed: the store [T, F, H, W] as paradis_assemble_batch /
+ * paradis_assemble_batch_packed take it (never written).  CSR lists, all DEVICE: ptr int64 [K + 1], rows int64 [N],
+ * w double [N]; cols int32 [C]: the store feature column of output channel c.  For slot k, channel c and pixel p, over
+ * the entries j in [ptr[k], ptr[k + 1]) whose value x[rows[j], cols[c], p] is finite (NaN and +-Inf are skipped per
+ * pixel; a packed store decodes "missing" to NaN):
+ *   S = sum_j w[j] * x,  Wt = sum_j w[j],  out[k, c, p] = (float)(S / Wt), NaN when Wt == 0
+ * S and Wt in double, in list order: no atomics, no zero fill, bit-identical run to run.  A row outside [0, T), a column
+ * outside [0, F) or a list bound outside [0, N] is CLAMPED (never read outside) and reported through *flag (DEVICE int,
+ * set to 1, never cleared).  One workgroup owns paradis_clim_mean_chunk() values of one (slot, channel) plane; when K * C
+ * * chunks exceeds the launch limit the slots are split over several launches.  K == 0 or C == 0 does nothing.
+ * rc 1 before any HIP call for a bad shape, a missing pointer, N < 0, or C * chunks above the launch limit.
+ * H*W % 4 == 0 with a 16-byte aligned out and a 16-byte (float32) / 8-byte (packed) aligned store takes 16 B / 8 B
+ * loads, anything else scalar loads with the same arithmetic per cell: the same bits either way.
+ * Algorithmic HBM bytes: N*C*H*W*(4 | 2) read + 4*K*C*H*W written.
+ *
+ * paradis_spherical_winds_inplace: the (x, y, z) planes of every wind triple of data [K, C, H, W] (fp32, dense) become
+ * (u, v, w), in place, by the expression of paradis_forecast_post (csrc/winds.h: one copy, the same bits).  units
+ * [n_units][8] int, plev and trig as paradis_forecast_post takes them; units_host: the same rows in host memory, checked
+ * (channels inside [0, C), levels inside [0, n_levels)) before any HIP call.  Rows of type 0 and level rows with x = -1
+ * are skipped; a level row reads its temperature channel (w = dr/dt * p g / (R T)).  A NaN in any of the three
+ * components gives NaN in all three.  K == 0 or n_units == 0 does nothing.
+ * Algorithmic HBM bytes per cell: 28 for a level row, 24 for the 10 m row. */
+int paradis_clim_mean_chunk(void);
+int paradis_clim_mean(const float* store, int64_t T, int F, int H, int W, const int64_t* ptr, const int64_t* rows,
+                      const double* w, int64_t N, int K, const int* cols, int C, float* out, int* flag, void* stream);
+int paradis_clim_mean_packed(const uint16_t* codes, const float* params, const int* domain, int64_t T, int F, int H,
+                             int W, const int64_t* ptr, const int64_t* rows, const double* w, int64_t N, int K,
+                             const int* cols, int C, float* out, int* flag, void* stream);
+int paradis_spherical_winds_inplace(float* data, const int* units, const int* units_host, int n_units,
+                                    const double* plev, int n_levels, const double* trig, int K, int C, int H, int W,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,10 @@ SIGNATURES = {
     "paradis_store_stats_ws_bytes": (S, [I, I, I, I]),
     "paradis_store_stats": (I, [P, I, P, I, I, I, I, I, I, I, P, I, P, P]),
     "paradis_cartesian_winds": (I, [P, I, P, I, P, P, I, P, I, I, I, P]),
+    "paradis_clim_mean_chunk": (I, []),
+    "paradis_clim_mean": (I, [P, L, I, I, I, P, P, P, L, I, P, I, P, P, P]),
+    "paradis_clim_mean_packed": (I, [P, P, P, L, I, I, I, P, P, P, L, I, P, I, P, P, P]),
+    "paradis_spherical_winds_inplace": (I, [P, P, P, I, P, I, P, I, I, I, I, P]),
 }
 
 _missing = []

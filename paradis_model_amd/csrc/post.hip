@@ -17,6 +17,7 @@
 // Algorithmic HBM bytes: 8*B*C*H*W (+ 4*B*L*H*W with the dew point).
 #include "common.h"
 #include "normalize.h"
+#include "winds.h"
 
 #pragma clang fp contract(off)
 
@@ -159,15 +160,9 @@ __global__ void __launch_bounds__(256) forecast_post_kernel(PostArgs a) {
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       const double slo = slon_t[x0 + j], clo = clon_t[x0 + j];
-      const double X = (double)wx.v[j], Y = (double)wy.v[j], Z = (double)wz.v[j];
-      ou.v[j] = (float)(-X * slo + Y * clo);
-      ov.v[j] = (float)(-X * sla * clo - Y * sla * slo + Z * cla);
-      if (type == U_LEVEL) {
-        const float rt = 287.05f * T.v[j];         // numpy: R * temperature stays float32
-        ow.v[j] = (float)((-X * cla * clo - Y * cla * slo - Z * sla) * (pg / (double)rt));
-      } else {
-        ow.v[j] = wz.v[j];                         // wind_z_10m keeps its de-normalised Cartesian value
-      }
+      // (wind_z_10m keeps its de-normalised Cartesian value; T is read for a level only)
+      spherical_wind(wx.v[j], wy.v[j], wz.v[j], type == U_LEVEL ? T.v[j] : 0.f, type == U_LEVEL, pg, sla, cla, slo,
+                     clo, ou.v[j], ov.v[j], ow.v[j]);
     }
     ou.store(dst + cx * P);
     ov.store(dst + cy * P);

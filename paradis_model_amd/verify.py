@@ -5,7 +5,7 @@ Conventions.  Forecast ``f`` and truth ``t`` are ``[B, C, H, W]`` fp32 in physic
 ``forecast.postprocess`` (with ``winds=True``: ``u, v, w`` where ``wind_x, wind_y, wind_z`` were).  ``w[h] >= 0`` are
 latitude weights (``[H]``, not all zero), ``Z = W * sum_h w[h]`` (formed in double on the host).  An optional
 climatology ``clim [K, C, H, W]`` comes with an index ``k[b]`` (int32 on the device, ``0 <= k < K``) that names the
-climatology slot of sample ``b`` at this lead.  Per sample ``b`` and channel ``c``, sums over the plane, with
+climatology slot of sample ``b`` at this lead (``climatology.build`` makes both from a ``DeviceStore``).  Per sample ``b`` and channel ``c``, sums over the plane, with
 ``fa = f - clim[k[b]]`` and ``ta = t - clim[k[b]]``::
 
     se = sum w (f-t)^2 / Z      e  = sum w (f-t) / Z      ae = sum w |f-t| / Z
