@@ -8,8 +8,9 @@
 //   NorMuon only: v <- beta2 v + (1-beta2) rowmean(X^2);  X <- X / (sqrt(v)+1e-8), rescaled to the
 //                 Frobenius norm it had before
 //   W <- W (1 - lr wd) - lr_adj X
-// dion runs the iteration in bf16 through Triton; here it is fp32 on the GEMMs of gemm.hip (exact f32 MFMA
-// or the bf16-split arithmetic, as the caller's pointwise GEMMs)
+// dion runs the iteration in bf16 through Triton; here it is fp32 on paradis_bgemm (gemm.hip: the C ABI and the choice of
+// a kernel), i.e. on the exact f32 MFMA kernels of gemm_exact.hip or the bf16-split kernels of gemm_split.hip, as the
+// caller's pointwise GEMMs
 // (a X + B X is computed as (B + a I) X, so the GEMM needs no scaled epilogue).  All scalars (norms)
 // stay on the device: no host synchronisation.
 #include <math.h>

@@ -3,7 +3,8 @@
 Every function takes and returns ``torch.float64`` tensors on whatever device its inputs live on, is a direct
 transcription of the mathematical definition (ATen ops only, gradients by autograd) and shares no code with the kernels
 or with ``oracle/``.  tests/test_refs64_cpu.py pins them to the reference goldens and to the fp32 oracle; the GPU sweep
-of tests/test_hip_kernel_edges.py measures the kernels against them."""
+of tests/test_hip_kernel_edges.py measures the kernels against them.  The Muon / NorMuon step at the end is dtype-generic
+and comes with the fp32 product orders that tests/test_hip_muon_edges.py uses as yardsticks."""
 import math
 
 import torch
@@ -143,3 +144,92 @@ def adamw_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay):
     denom = v.sqrt() / math.sqrt(bc2) + eps
     p = p - (lr / bc1) * (m / denom)
     return p, m, v
+
+
+# ---------------------------------------------------------------------------------------------- Muon / NorMuon
+# Dtype-generic (the one exception to "float64 only" in this file): evaluated in float64 it is the reference of
+# csrc/muon.hip, evaluated in float32 with one of the product orders below it is the yardstick "an ordinary fp32
+# evaluation of the same algorithm" that tests/test_hip_muon_edges.py measures the kernels against.
+NS_COEFFS = ((4.0848, -6.8946, 2.9270), (3.9505, -6.3029, 2.6377), (3.7418, -5.5913, 2.3037),
+             (2.8769, -3.1427, 1.2046), (2.8366, -3.0525, 1.2012))
+
+
+def matmul_k16(a, b):
+    """a @ b with the k axis taken in chunks of 16 whose partial products are accumulated in order (the k depth of the
+    MFMA tiles)"""
+    a, b = a.contiguous(), b.contiguous()
+    acc = torch.zeros(a.shape[0], b.shape[1], dtype=a.dtype)
+    for k in range(0, a.shape[1], 16):
+        acc = acc + a[:, k:k + 16] @ b[k:k + 16]
+    return acc
+
+
+def matmul_seq(a, b):
+    """a @ b strictly sequential over k: rank-1 updates, every product rounded before it is added (the least favourable
+    ordinary order)"""
+    a, b = a.contiguous(), b.contiguous()
+    acc = torch.zeros(a.shape[0], b.shape[1], dtype=a.dtype)
+    for k in range(a.shape[1]):
+        acc = acc + a[:, k, None] * b[k, None, :]
+    return acc
+
+
+def _bf16_terms(x):
+    h = x.bfloat16().float()
+    r = x - h
+    m = r.bfloat16().float()
+    return h, m, (r - m).bfloat16().float()
+
+
+def matmul_bf16x3(a, b):
+    """CPU emulation of the bf16x3 arithmetic (csrc/gemm_common.h): each fp32 operand is h + m + l in bfloat16 (round to
+    nearest even, exact), the six partial products of weight >= 2^-16 are kept (m.m, l.h, h.l, m.h, h.m, h.h, smallest
+    first, per 16-deep k tile) and accumulated in float32.  The products of two bfloat16 numbers are exact in float32."""
+    assert a.dtype == torch.float32 and b.dtype == torch.float32
+    ah, am, al = _bf16_terms(a.contiguous())
+    bh, bm, bl = _bf16_terms(b.contiguous())
+    acc = torch.zeros(a.shape[0], b.shape[1], dtype=torch.float32)
+    for k in range(0, a.shape[1], 16):
+        s = slice(k, k + 16)
+        for p, q in ((am, bm), (al, bh), (ah, bl), (am, bh), (ah, bm), (ah, bh)):
+            acc = acc + p[:, s] @ q[s]
+    return acc
+
+
+def muon_momentum(g, m, mu, nesterov):
+    """m <- mu m + g; returns (m_new, the matrix that is orthogonalised)"""
+    m = mu * m + g
+    return m, (g + mu * m if nesterov else m)
+
+
+def newton_schulz(u, eps, matmul=torch.matmul, coeffs=NS_COEFFS):
+    """Five quintic Newton-Schulz iterations on u / (||u||_F + eps), on the wide orientation; result in u's orientation"""
+    tall = u.shape[0] > u.shape[1]
+    x = u.mT if tall else u
+    x = x / (x.norm() + eps)
+    for a, b, c in coeffs:
+        A = matmul(x, x.mT)
+        B = b * A + c * matmul(A, A)
+        x = a * x + matmul(B, x)
+    return x.mT if tall else x
+
+
+def muon_apply(w, x, v, *, lr, lr_adj, beta2, weight_decay):
+    """The part of the step behind the orthogonalisation x: NorMuon's per-row second moment (v is not None; [rows, 1]),
+    the rescale to the Frobenius norm x had, decoupled weight decay.  Returns (w_new, v_new, u)."""
+    u = x
+    if v is not None:
+        norm_x = x.norm()
+        v = beta2 * v + (1 - beta2) * (x * x).mean(dim=-1, keepdim=True)
+        u = x / (v.sqrt() + 1e-8)
+        u = u * (norm_x / u.norm().clamp(min=1e-8))
+    return w * (1 - lr * weight_decay) - lr_adj * u, v, u
+
+
+def muon_step(w, g, m, v, *, lr, lr_adj, mu, beta2, weight_decay, eps, nesterov, matmul=torch.matmul, coeffs=NS_COEFFS):
+    """One Muon (v is None) or NorMuon (v: [rows, 1]) update of a [rows, cols] matrix; lr_adj is the shape-adjusted
+    learning rate.  Returns (w_new, m_new, v_new, u), u = the orthogonalised update in the matrix's own orientation."""
+    m, o = muon_momentum(g, m, mu, nesterov)
+    w, v, u = muon_apply(w, newton_schulz(o, eps, matmul, coeffs), v, lr=lr, lr_adj=lr_adj, beta2=beta2,
+                         weight_decay=weight_decay)
+    return w, m, v, u

@@ -71,15 +71,15 @@ def test_device_lr_equals_host_lr(cls_name, nesterov, split, monkeypatch):
     same fp32 learning rate as a host scalar, on cloned inputs.  Per matrix: max|dw| <= 1e-6 max|update| + twin spread,
     the twin spread being the difference between identical calls of the host-scalar entry.
 
-    The norm sums of the step use float atomics, so identical calls land on one of a few outcomes one ulp of ``w``
-    apart (measured on (130, 258): five different sums of squares over eleven identical calls, the weights 0, 1.5e-8 or
-    3.0e-8 apart), and 1e-6 max|update| (9e-10 there) is below that ulp: one pair of host calls and one device call
-    compare outcomes of that lottery, not the two entries (a first version of this test did, and failed on
-    (130, 258) with a device-vs-host difference and a twin spread that were both 0 or 3.0e-8 from run to run).  So each
-    entry is called N_TWINS times: the twin spread is the largest difference among the host calls, the device-vs-host
-    difference the smallest over all pairs of a device and a host call - a systematic error of the device-side
-    coefficients is in every such pair.  A device learning rate of 0 leaves the weights bit-unchanged whatever the
-    weight decay."""
+    When this test was written the norm sums of the step used float atomics, and identical calls landed on one of a few
+    outcomes one ulp of ``w`` apart; the twin spread allowed for that.  The sums are now reduced in a fixed order
+    (muon.hip, block_sum_fixed: per-workgroup partials added the same way by every consumer), so identical calls give
+    identical bits - tests/test_hip_muon_edges.py::test_two_identical_steps_give_identical_bits holds the kernel to
+    it - and the twin spread is expected to be 0.  The procedure is kept as it was: each entry is called N_TWINS times,
+    the twin spread is the largest difference among the host calls, the device-vs-host difference the smallest over
+    all pairs of a device and a host call - a systematic error of the device-side coefficients is in every such pair,
+    and 1e-6 max|update| stays the bound on it.  A device learning rate of 0 leaves the weights bit-unchanged whatever
+    the weight decay."""
     from paradis_model_amd import _lib, ops, optim
     monkeypatch.setattr(ops, "GEMM_SCHEME", ops.GEMM_BF16X3 if split else ops.GEMM_EXACT)
     calls = {"muon_step": 0, "muon_step_d": 0}

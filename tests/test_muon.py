@@ -2,7 +2,8 @@
 the un-vendored, un-pinned `dion` package; the oracle restates the published algorithm.  The CPU
 tests check the oracle's defining properties and the host-side grouping; the GPU tests check the
 HIP step against the oracle (fp32 on both sides, 2e-4 of the update's magnitude: five Newton-Schulz
-iterations amplify GEMM summation-order differences)."""
+iterations amplify GEMM summation-order differences).
+The tight bound - fp64 reference, fp32 yardsticks, every grid and tile edge - lives in tests/test_hip_muon_edges.py."""
 import pytest
 import torch
 

@@ -209,3 +209,74 @@ def test_adamw_reference_is_torch_adamw_in_fp64():
     for r, (p, m, v) in zip(ref, mine):
         st = opt.state[r]
         assert max_rel(p, r) <= 1e-14 and max_rel(m, st["exp_avg"]) <= 1e-14 and max_rel(v, st["exp_avg_sq"]) <= 1e-14
+
+
+# ---------------------------------------------------------------------------------------------- Muon / NorMuon
+def test_muon_reference_is_the_oracle_in_fp64():
+    """(a) fp64 R.muon_step == oracle.muon_oracle.muon_step evaluated in fp64, to 1e-12: Muon and NorMuon, Nesterov on and
+    off, a wide, a tall and a one-row matrix."""
+    from oracle import muon_oracle as MO
+    for si, shape in enumerate(((24, 40), (40, 24), (1, 40))):
+        for normuon in (False, True):
+            for nesterov in (False, True):
+                w, g, m = (seeded(10 * si + k, *shape).double() for k in range(3))
+                v = (seeded(10 * si + 3, shape[0], 1, kind="rand").abs() + 0.5).double() / max(shape) if normuon else None
+                adjust = "rms_norm" if normuon else "spectral_norm"
+                mo, vo = m.clone(), None if v is None else v.clone()
+                wo = MO.muon_step(w, g, mo, lr=5e-3, mu=0.95, weight_decay=0.01, eps=1e-8, nesterov=nesterov,
+                                  adjust=adjust, V=vo, beta2=0.95)
+                wn, mn, vn, _ = R.muon_step(w, g, m, v, lr=5e-3, lr_adj=MO.adjusted_lr(5e-3, shape, adjust), mu=0.95,
+                                            beta2=0.95, weight_decay=0.01, eps=1e-8, nesterov=nesterov)
+                assert max_rel(wn, wo) <= 1e-12 and max_rel(mn, mo) <= 1e-12, (shape, normuon, nesterov)
+                assert vn is None or max_rel(vn, vo) <= 1e-12
+    assert R.NS_COEFFS == MO.NS_COEFFS
+
+
+def test_muon_product_orders_are_fp32_products():
+    """the three orders and the bf16x3 emulation against the fp64 product: fp32 level (a K = 300 dot product of N(0,1)
+    terms: 2e-6 is the bound of tests/test_hip_gemm_split.py); exact on small integers"""
+    from tests import _muon_cases as C
+    a, b = seeded(1, 37, 300), seeded(2, 300, 41)
+    ref = a.double() @ b.double()
+    for name, mm in C.ORDERS.items():
+        assert max_rel(mm(a, b), ref) <= 2e-6, name
+    g = torch.Generator().manual_seed(3)
+    a, b = torch.randint(-8, 9, (5, 40), generator=g).float(), torch.randint(-8, 9, (40, 7), generator=g).float()
+    for name, mm in C.ORDERS.items():
+        assert torch.equal(mm(a, b).double(), a.double() @ b.double()), name
+
+
+def test_muon_fp32_yardsticks_stay_under_the_ceiling():
+    """(b) at every matrix of the GPU cases (tests/_muon_cases.py) the update seen through w = 0, and NorMuon's v, of each
+    of the four fp32 evaluations sit under the 1e-5 ceiling the kernels are held to: the ceiling is not one the reference
+    side itself would miss."""
+    from tests import _muon_cases as C
+    worst = 0.0
+    for rows, cols, member, nesterov in C.matrices():
+        for normuon in (False, True):
+            r = C.refs(rows, cols, member, nesterov, normuon, w_zero=True)
+            for name, (w, v) in r["cpu"].items():
+                e = [C.err(w, r["w64"])] + ([C.err(v, r["v64"])] if normuon else [])
+                worst = max([worst] + e)
+                assert max(e) <= C.CEILING, ((rows, cols, member, nesterov), normuon, name, e)
+    r = C.refs(33, 31, 0, False, True, w_zero=True, v_zero=True)          # the first NorMuon step: v = 0 going in
+    for name, (w, v) in r["cpu"].items():
+        assert max(C.err(w, r["w64"]), C.err(v, r["v64"])) <= C.CEILING, ("first step", name)
+    print(f"largest e_cpu of the update / v over all matrices: {worst:.2e}")
+
+
+def test_muon_bound_sees_a_wrong_coefficient():
+    """(c) a fourth-digit typo in one Newton-Schulz coefficient (2.8769 -> 2.8766) moves the fp64 update by more than ten
+    times the ceiling at a small, a mid-sized and the largest shape (1.2e-4 .. 2.2e-4).  A matrix of rank one (1 x 40,
+    40 x 1) has a single singular value, which the fifth iteration pulls back towards its fixed point: 3.8e-5 there,
+    still above the ceiling (asserted: three times)."""
+    from tests import _muon_cases as C
+    typo = tuple((2.8766, b, c) if a == 2.8769 else (a, b, c) for a, b, c in R.NS_COEFFS)
+    assert typo != R.NS_COEFFS
+    for rows, cols, member, nesterov, factor in [(33, 31, 0, False, 10), (64, 96, 0, True, 10), (513, 520, 0, True, 10),
+                                                 (1, 40, 0, False, 3), (40, 1, 0, True, 3)]:
+        i = C.inputs(rows, cols, member)
+        _, o = R.muon_momentum(i["g"].double(), i["m"].double(), C.MU, nesterov)
+        moved = C.err(R.newton_schulz(o, C.EPS, coeffs=typo), C.orth(rows, cols, member, nesterov)["x64"])
+        print(f"typo moves {rows}x{cols} by {moved:.2e}")
+        assert moved > factor * C.CEILING, ((rows, cols), moved)
