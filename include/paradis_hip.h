@@ -704,6 +704,42 @@ int paradis_spherical_winds_inplace(float* data, const int* units, const int* un
                                     const double* plev, int n_levels, const double* trig, int K, int C, int H, int W,
                                     void* stream);
 
+/* ---- Zonal power spectra of forecast and truth (ABI 10, additive), csrc/spectrum.hip: at which scales a forecast has
+ * gone wrong.  The project's own definition, in the spirit of WeatherBench-2's ZonalEnergySpectrum; not pinned against it.
+ * One launch pair on `stream`, no host synchronisation, no memset or copy nodes, no atomics (bit-identical run to run);
+ * neither input is written.
+ *   fc, truth [B, C, H, W] fp32 in physical units, dense [C, H, W] states, batch strides fc_bs / truth_bs in elements;
+ *   channels int32 [Cs] (DEVICE): the plane of output channel cs (only these planes are read; an entry outside [0, C)
+ *   is not read and turns its sums into NaN), or NULL with Cs == C;
+ *   band_w double [R][H] >= 0 (DEVICE), band_wsum double [R] = sum_h band_w[r][h] > 0 (DEVICE, formed by the caller);
+ *   twiddle float [W][2] (DEVICE) = exp(-2 pi i j / W), j < W, computed in double by the caller and rounded once.
+ * Per row h, W even, K = W / 2, k = 0 .. K, m_k = 1 for k in {0, K}, else 2:
+ *   X[h,k] = (1/W) sum_i x[h,i] exp(-2 pi i k i / W),  pf = m_k |F|^2,  pt = m_k |T|^2,  co = m_k Re(F conj T)
+ *   S[r,k] = sum_h band_w[r][h] p[h,k] / band_wsum[r] over the rows with band_w[r][h] != 0 (a row of weight 0 is left
+ *   out, not multiplied in; a row of weight 0 in every band is neither read nor transformed)
+ *   acc[cs][r][k][0..2] += {S_ff, S_tt, S_ft} per sample in b order, the row groups of a sample in index order;
+ *   count[0] += B.  Two calls of B samples give the bits of one call of the 2B batch.
+ * acc: DEVICE double [Cs][R][K + 1][3] and count: DEVICE double [1], the rows of this lead, ordinary read-modify-write
+ * (calls on one stream are ordered).  Non-finite inputs are not masked.
+ * Forecast and truth rows go through ONE complex fp32 transform of z = (f - p) + i (t - p), p = truth[h][0] (restored
+ * at k = 0 in double); everything after the transform is double.  paradis_spectrum_schedule(W): 1 = fft (W even, a
+ * product of 2, 3 and 5, W <= paradis_spectrum_fft_max_w(): Stockham mixed radix in LDS), 2 = direct (any other even
+ * W <= paradis_spectrum_direct_max_w(): an O(W^2) row DFT out of LDS, summed in double), 0 = refused.  A workgroup owns
+ * paradis_spectrum_rows() rows of one plane.
+ * ws: paradis_spectrum_ws_bytes(B, Cs, H, W, R) bytes, 8-byte aligned: double [B*Cs][ceil(H / paradis_spectrum_rows())]
+ * [R][3][K + 1].  B == 0 does nothing.  rc 1 before any HIP call for: B < 0 or C / Cs / H / W < 1, a refused W, R outside
+ * [1, 64] or more bands than the LDS holds at this W (24 * R * (K + 1) bytes beside the transform's buffers), channels
+ * NULL with Cs != C, a NULL acc / count / ws / input, batch strides shorter than a state, a grid above the launch limit.
+ * Algorithmic HBM bytes: 8 * B * Cs * H * W (less the rows of weight 0 in every band). */
+int paradis_spectrum_rows(void);
+int paradis_spectrum_fft_max_w(void);
+int paradis_spectrum_direct_max_w(void);
+int paradis_spectrum_schedule(int W);
+size_t paradis_spectrum_ws_bytes(int B, int Cs, int H, int W, int R);
+int paradis_spectrum_update(const float* fc, int64_t fc_bs, const float* truth, int64_t truth_bs, const int* channels,
+                            int Cs, const double* band_w, const double* band_wsum, const float* twiddle, double* acc,
+                            double* count, void* ws, int B, int C, int H, int W, int R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,12 @@ SIGNATURES = {
     "paradis_clim_mean": (I, [P, L, I, I, I, P, P, P, L, I, P, I, P, P, P]),
     "paradis_clim_mean_packed": (I, [P, P, P, L, I, I, I, P, P, P, L, I, P, I, P, P, P]),
     "paradis_spherical_winds_inplace": (I, [P, P, P, I, P, I, P, I, I, I, I, P]),
+    "paradis_spectrum_rows": (I, []),
+    "paradis_spectrum_fft_max_w": (I, []),
+    "paradis_spectrum_direct_max_w": (I, []),
+    "paradis_spectrum_schedule": (I, [I]),
+    "paradis_spectrum_ws_bytes": (S, [I, I, I, I, I]),
+    "paradis_spectrum_update": (I, [P, L, P, L, P, I, P, P, P, P, P, P, I, I, I, I, I, P]),
 }
 
 _missing = []
