@@ -740,6 +740,39 @@ int paradis_spectrum_update(const float* fc, int64_t fc_bs, const float* truth, 
                             int Cs, const double* band_w, const double* band_wsum, const float* twiddle, double* acc,
                             double* count, void* ws, int B, int C, int H, int W, int R, void* stream);
 
+/* ---- Event verification (ABI 10, additive), csrc/events.hip: per lead, event source and latitude row the integer 2x2
+ * contingency counts of "value beyond a threshold" in forecast against truth.  One launch pair on `stream`, no host
+ * synchronisation, no memset or copy nodes, no atomics, no float arithmetic after the decision: the counts are exact.
+ *   fc, truth [B, C, H, W] fp32 in physical units, dense [C, H, W] states, batch strides fc_bs / truth_bs in elements;
+ *   clim [K, C, H, W] fp32 dense and clim_index [B] int32 (DEVICE), or both NULL;
+ *   src_table HOST int32 [S][4] = {kind, c0, c1, nthr}: kind 0 plain x = v[c0]; 1 speed x = sqrtf(v[c0]^2 + v[c1]^2)
+ *   (fp32: mul, mul, add, sqrt, uncontracted); 2 anomaly x = v[c0] - clim[clim_index[b]][c0] (one fp32 subtraction);
+ *   thr_table HOST float [S][1 + paradis_events_max_thresholds()] = {sign, thr'[0 .. nthr)}: the event is
+ *   sign * x >= thr'[j], sign = +1 or -1 ("x <= thr" is sign = -1, thr' = -thr).  Both tables are read on the host and
+ *   travel as kernel arguments (a captured launch keeps their values); S <= paradis_events_max_sources().
+ * A cell is valid for a source iff every value it reads is finite (forecast and truth, both components of a speed, the
+ * climatology cell of an anomaly); a sample whose clim_index is outside [0, K) has no valid cell for anomaly sources
+ * and nothing of that slot is read.  Invalid cells are counted in no class.
+ *   acc_lead: DEVICE int64 [S][H][1 + 3 TMAX], the row of this lead: {nV, nF[TMAX], nO[TMAX], nFO[TMAX]} += the counts of
+ *   valid cells, forecast events, truth events and joint events (entries past nthr stay as they are: += 0);
+ *   n_samples_lead: DEVICE int64 [1] += B.  Ordinary read-modify-writes (calls on one stream are ordered).
+ * A workgroup owns paradis_events_rows(W) ~ 8192 / W (>= 1) whole rows of one (sample, source); only the planes of the
+ * sources are read.  ws: paradis_events_ws_bytes(B, S, H, W) bytes, 4-byte aligned: uint32 [B][S][H][1 + 3 TMAX].
+ * B == 0 does nothing.  rc 1 before any HIP call for: B < 0, C / S / H / W < 1, S above the limit, H W >= 2^31 - 8192,
+ * a grid above the launch limit, batch strides shorter than a state, clim without clim_index or the reverse, K < 1
+ * with a climatology, an anomaly source without a climatology, a kind outside 0 .. 2, channels outside [0, C), nthr
+ * outside [1, TMAX], a sign that is not +-1, a NULL acc_lead, n_samples_lead, ws or table.
+ * W % 4 == 0 with 16-byte aligned bases and strides takes 16-byte loads, anything else scalar loads: the same counts.
+ * Algorithmic HBM bytes per cell of a source: 8 plain, 16 speed, 12 anomaly. */
+int paradis_events_max_thresholds(void);
+int paradis_events_max_sources(void);
+int paradis_events_rows(int W);
+size_t paradis_events_ws_bytes(int B, int S, int H, int W);
+int paradis_events_update(const float* fc, int64_t fc_bs, const float* truth, int64_t truth_bs, const float* clim,
+                          const int* clim_index, int K, const int* src_table, const float* thr_table,
+                          int64_t* acc_lead, int64_t* n_samples_lead, void* ws, int B, int C, int S, int H, int W,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

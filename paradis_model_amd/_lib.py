@@ -144,6 +144,11 @@ SIGNATURES = {
     "paradis_spectrum_schedule": (I, [I]),
     "paradis_spectrum_ws_bytes": (S, [I, I, I, I, I]),
     "paradis_spectrum_update": (I, [P, L, P, L, P, I, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "paradis_events_max_thresholds": (I, []),
+    "paradis_events_max_sources": (I, []),
+    "paradis_events_rows": (I, [I]),
+    "paradis_events_ws_bytes": (S, [I, I, I, I]),
+    "paradis_events_update": (I, [P, L, P, L, P, P, I, P, P, P, P, P, I, I, I, I, I, P]),
 }
 
 _missing = []

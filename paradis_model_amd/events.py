@@ -1,0 +1,384 @@
+"""Event verification: did the forecast put the event where it happened?  Per lead time, event source, latitude band and
+threshold the 2x2 contingency table of "value beyond a threshold" in forecast against truth, counted on the device in
+integers, and the categorical scores that come from it (POD, FAR, POFD, CSI, frequency bias, base rate, ETS, HSS, SEDI).
+
+The definitions are the project's own, textbook formulas; they are NOT pinned against any package.  The tests pin the
+kernel against a plain numpy restatement (tests/events_oracle.py) - exactly: the event decision is discrete and the
+counts are integers, so the device result equals the restatement bit for bit, not within a bound.
+
+Conventions.  Forecast ``f`` and truth ``t`` are ``[B, C, H, W]`` fp32 in physical units, in the chunk layout of
+``forecast.postprocess`` (``PostSpec.names``).  An event source yields one fp32 value ``x`` per cell::
+
+    "name"                        plain     x = v[c]
+    ("speed", "name_a", "name_b") speed     x = sqrtf(a*a + b*b)             (fp32: mul, mul, add, sqrt, uncontracted)
+    ("anomaly", "name")           anomaly   x = v[c] - clim[k[b]][c]         (one fp32 subtraction)
+
+with 1 to ``paradis_events_max_thresholds()`` thresholds in physical units (rounded to fp32; they need not be sorted)
+and a direction: ``"ge"`` (event: ``x >= thr``) or ``"le"`` (``x <= thr``; handed to the kernel as ``sign = -1``,
+``thr' = -thr``, which is exact).  ``x == thr`` is an event in both directions, ``-0.0 >= 0.0`` is one.
+
+A cell is valid for a source iff every input value it reads is finite: forecast and truth, both components of a speed
+source, the climatology cell of an anomaly source.  A sample whose ``clim_index`` is outside ``[0, K)`` has no valid cell
+for anomaly sources (nothing of that slot is read).  INVALID CELLS ARE COUNTED IN NO CLASS.  This departs from
+``verify.Scorecard`` and ``spectrum.Spectra``, where non-finite values propagate into the scores: a count cannot carry a
+NaN.  ``valid_fraction`` reports how much was counted.
+
+Per valid cell and threshold ``j``, ``F``: the forecast is beyond the threshold, ``O``: the truth is.  The device keeps,
+per (lead, source, latitude row ``h``), ``nV`` (valid cells) and ``nF[j]``, ``nO[j]``, ``nFO[j]``: the int64 accumulator
+``acc [n_leads, S, H, 1 + 3 * TMAX]`` and ``n_samples`` int64 ``[n_leads]``.  Weights never enter the kernel:
+``result`` applies the band and latitude weights ``wb[r, h]`` to the integer rows on the host, in numpy float64::
+
+    hits a = sum_h wb nFO      false alarms b = sum_h wb (nF - nFO)      misses c = sum_h wb (nO - nFO)
+    correct negatives d = sum_h wb (nV - nF - nO + nFO)                  n = a + b + c + d
+
+    pod = a/(a+c)   far = b/(a+b)   pofd = b/(b+d)   csi = a/(a+b+c)   frequency_bias = (a+b)/(a+c)   base_rate = (a+c)/n
+    ets = (a - ar)/(a+b+c - ar),  ar = (a+b)(a+c)/n          hss = 2(ad - bc)/((a+c)(c+d) + (a+b)(b+d))
+    sedi = (ln pofd - ln pod - ln(1-pofd) + ln(1-pod)) / (ln pofd + ln pod + ln(1-pofd) + ln(1-pod))
+
+A zero denominator or a ``ln 0`` gives NaN.
+
+One launch pair per ``update`` (``csrc/events.hip``) reads only the planes of the chosen sources, once.
+
+No CPU fallback: ``update`` needs tensors on the HIP device.  Everything else (argument checks, ``counts``, ``result``,
+``scores``, ``table``) works on any device.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import dptr, require_hip, stream_ptr
+from ._tables import batch_stride, dense_state, sum_over_ranks, workspace
+from .spectrum import band_weights
+
+KINDS = {"plain": 0, "speed": 1, "anomaly": 2}
+BYTES_PER_CELL = {0: 8, 1: 16, 2: 12}          # forecast and truth (and climatology) values of one cell
+TABLES = ("hits", "false_alarms", "misses", "correct_negatives")
+SCORES = ("pod", "far", "pofd", "csi", "frequency_bias", "base_rate", "ets", "hss", "sedi")
+
+
+def max_thresholds() -> int:
+    return int(_lib.lib.paradis_events_max_thresholds())
+
+
+def _ratio(num, den):
+    """``num / den``, NaN where ``den == 0``"""
+    ok = den != 0
+    return np.where(ok, num / np.where(ok, den, 1.0), np.nan)
+
+
+def _ln(x):
+    """``ln x``, NaN where ``x <= 0`` (a ``ln 0`` is NaN here, not -inf)"""
+    ok = x > 0
+    return np.where(ok, np.log(np.where(ok, x, 1.0)), np.nan)
+
+
+def scores(a, b, c, d) -> dict:
+    """the nine scores of 2x2 tables (hits ``a``, false alarms ``b``, misses ``c``, correct negatives ``d``: arrays of one
+    shape, or numbers), float64; a zero denominator or a ``ln 0`` gives NaN, without warnings.  Host only."""
+    a, b, c, d = (np.asarray(v, np.float64) for v in (a, b, c, d))
+    with np.errstate(all="ignore"):
+        n = a + b + c + d
+        pod, pofd = _ratio(a, a + c), _ratio(b, b + d)
+        ar = _ratio((a + b) * (a + c), n)
+        lf, lh, l1f, l1h = _ln(pofd), _ln(pod), _ln(1.0 - pofd), _ln(1.0 - pod)
+        return {"pod": pod, "far": _ratio(b, a + b), "pofd": pofd, "csi": _ratio(a, a + b + c),
+                "frequency_bias": _ratio(a + b, a + c), "base_rate": _ratio(a + c, n),
+                "ets": _ratio(a - ar, a + b + c - ar),
+                "hss": _ratio(2.0 * (a * d - b * c), (a + c) * (c + d) + (a + b) * (b + d)),
+                "sedi": _ratio(lf - lh - l1f + l1h, lf + lh + l1f + l1h)}
+
+
+class EventTable:
+    """Per-lead contingency tables of threshold events, accumulated on the device (module docstring for the definitions;
+    invalid - non-finite - cells are counted in no class, unlike ``Scorecard``, where NaN propagates).
+
+    ``names``: the chunk's channel names (``PostSpec.names``); ``lat_deg``: ``[H]`` latitudes in degrees; ``events``: a
+    dict label -> ``{"source": "name" | ("speed", a, b) | ("anomaly", name), "thresholds": [1 .. TMAX finite numbers],
+    "direction": "ge" | "le"}`` (direction defaults to ``"ge"``), at most ``paradis_events_max_sources()`` entries; a
+    speed of one channel with itself is refused.  ``bands`` and ``weights`` as in ``spectrum.Spectra``: a dict name ->
+    ``(lat_lo, lat_hi)`` in degrees, inclusive (default ``{"global": (-90, 90)}``), row weights ``weights[h]`` inside a
+    band and 0 outside (default ``cos(lat)``, pole rows 0).  ``climatology``: ``[K, C, H, W]`` fp32 on the device, as in
+    ``Scorecard``; anomaly sources need one.
+
+    ``acc`` is the int64 ``[n_leads, S, H, 1 + 3 * TMAX]`` accumulator on ``device`` - ``{nV, nF[TMAX], nO[TMAX],
+    nFO[TMAX]}`` per row -, ``n_leads * S * H * 200`` bytes: 35 MB at 721 rows, 6 sources and 40 leads, a few KB per lead
+    at 32 x 64.  ``n_samples`` is int64 ``[n_leads]``.
+
+    ``update(lead, forecast, truth, clim_index=None)``: one launch pair on the current stream, no host synchronisation,
+    graph-capturable, neither input is written; ``forecast`` / ``truth`` ``[B, C, H, W]`` fp32 with dense ``[C, H, W]``
+    states and any batch stride; ``clim_index`` ``[B]`` int32 on the device (optional with a one-slot climatology).
+    ``counts(sync_dist=False)``: one device read (after ONE all-reduce of the int64 accumulators with ``sync_dist``);
+    the raw integers ``valid [n_leads, S, H]``, ``forecast_yes``, ``observed_yes``, ``both [n_leads, S, H, T]`` (``T``:
+    the longest threshold list; entries past a source's own list are -1) and ``n_samples [n_leads]``.
+    ``result(sync_dist=False)``: float64 ``hits``, ``false_alarms``, ``misses``, ``correct_negatives`` and the nine
+    ``SCORES``, each ``[n_leads, S, R, T]`` (NaN past a source's thresholds and for leads never updated),
+    ``valid_fraction [n_leads, S, R]`` (the weighted share of the cells seen that were valid), ``count [n_leads]``,
+    ``labels``, ``thresholds`` (per label, as given, after rounding to fp32), ``directions`` and ``bands``.
+    ``scores(a, b, c, d)``: host only, tables -> the nine scores.  ``table(result, label, ...)``: plain text for logs.
+    ``reset()`` clears the accumulators."""
+
+    def __init__(self, names: Sequence[str], lat_deg, n_leads: int, events: dict, *, bands: Optional[dict] = None,
+                 weights=None, climatology: Optional[torch.Tensor] = None, device="cuda"):
+        self.names = [str(n) for n in names]
+        C = len(self.names)
+        if C < 1:
+            raise ValueError("EventTable: names must list at least one channel")
+        if isinstance(n_leads, bool) or int(n_leads) != n_leads or int(n_leads) < 1:
+            raise ValueError(f"EventTable: n_leads must be an integer >= 1, got {n_leads!r}")
+        self.n_leads = int(n_leads)
+        self.device = torch.device(device)
+        lat = torch.as_tensor(lat_deg).detach().reshape(-1).double().cpu().numpy()
+        H = lat.size
+        if H < 1 or not np.isfinite(lat).all() or np.abs(lat).max() > 90.0:
+            raise ValueError("EventTable: lat_deg must be a vector [H] of finite latitudes in [-90, 90] degrees")
+        if weights is None:
+            w64 = np.clip(np.cos(np.deg2rad(lat)), 0.0, None)           # (cos(+-90 deg) in double is 6e-17, not 0)
+            w64[np.abs(lat) == 90.0] = 0.0
+        else:
+            w = torch.as_tensor(weights).detach().reshape(-1)
+            if w.numel() != H or not w.is_floating_point():
+                raise ValueError(f"EventTable: weights must be a floating-point vector [{H}]")
+            w64 = w.double().cpu().numpy()
+            if not np.isfinite(w64).all() or (w64 < 0).any() or not w64.sum() > 0.0:
+                raise ValueError("EventTable: weights must be finite, >= 0 and not all zero")
+        if bands is None:
+            bands = {"global": (-90.0, 90.0)}
+        if not isinstance(bands, dict) or len(bands) < 1:
+            raise ValueError("EventTable: bands must be a non-empty dict name -> (lat_lo, lat_hi)")
+        self.bands = [str(b) for b in bands]
+        try:
+            self.band_w = band_weights(lat, w64, bands)                  # double [R, H], on the host
+        except ValueError as e:
+            raise ValueError(str(e).replace("Spectra:", "EventTable:")) from None
+        self.H = H
+        self.W: Optional[int] = None
+        self.climatology = None
+        if climatology is not None:
+            cl = climatology
+            if not isinstance(cl, torch.Tensor) or cl.dim() != 4 or cl.dtype != torch.float32 or \
+                    cl.shape[0] < 1 or cl.shape[1] != C or cl.shape[2] != H or not cl.is_contiguous():
+                raise ValueError(f"EventTable: climatology must be a contiguous float32 [K, {C}, {H}, W] tensor")
+            if cl.device.type != self.device.type:
+                raise ValueError(f"EventTable: climatology lives on {cl.device}, the table on {self.device}")
+            self.climatology = cl
+        self._parse(events)
+        S = len(self.labels)
+        with torch.inference_mode(False):
+            self.acc = torch.zeros(self.n_leads, S, H, 1 + 3 * self.tmax, dtype=torch.int64, device=self.device)
+            self.n_samples = torch.zeros(self.n_leads, dtype=torch.int64, device=self.device)
+        self._ws: Dict[tuple, torch.Tensor] = {}      # (device, stream) -> workspace
+        self._slot0: Dict[int, torch.Tensor] = {}     # B -> zeros [B] int32: the index of a one-slot climatology
+
+    def _channel(self, label, name) -> int:
+        if not isinstance(name, str) or name not in self.names:
+            raise ValueError(f"EventTable: event '{label}': channel {name!r} is not among the names")
+        return self.names.index(name)
+
+    def _parse(self, events) -> None:
+        """labels, kinds, thresholds, directions and the two host tables of the entry point"""
+        self.tmax = max_thresholds()
+        smax = int(_lib.lib.paradis_events_max_sources())
+        if not isinstance(events, dict) or len(events) < 1:
+            raise ValueError("EventTable: events must be a non-empty dict label -> {source, thresholds, direction}")
+        if len(events) > smax:
+            raise ValueError(f"EventTable: {len(events)} events, at most {smax} go into one table")
+        self.labels: List[str] = []
+        self.thresholds: List[List[float]] = []
+        self.directions: List[str] = []
+        src = np.zeros((len(events), 4), np.int32)
+        thr = np.zeros((len(events), 1 + self.tmax), np.float32)
+        for s, (label, ev) in enumerate(events.items()):
+            label = str(label)
+            if not isinstance(ev, dict) or "source" not in ev or "thresholds" not in ev or \
+                    set(ev) - {"source", "thresholds", "direction"}:
+                raise ValueError(f"EventTable: event '{label}' must be a dict with source, thresholds and, optionally, "
+                                 f"direction")
+            source = ev["source"]
+            if isinstance(source, str):
+                kind, c0, c1 = KINDS["plain"], self._channel(label, source), 0
+            elif isinstance(source, (tuple, list)) and len(source) == 3 and source[0] == "speed":
+                kind, c0, c1 = KINDS["speed"], self._channel(label, source[1]), self._channel(label, source[2])
+                if c0 == c1:
+                    raise ValueError(f"EventTable: event '{label}': the speed of '{source[1]}' with itself is refused "
+                                     f"(take the plain channel with both directions instead)")
+            elif isinstance(source, (tuple, list)) and len(source) == 2 and source[0] == "anomaly":
+                kind, c0, c1 = KINDS["anomaly"], self._channel(label, source[1]), 0
+                if self.climatology is None:
+                    raise ValueError(f"EventTable: event '{label}' is an anomaly, but the table has no climatology")
+            else:
+                raise ValueError(f"EventTable: event '{label}': source must be 'name', ('speed', a, b) or "
+                                 f"('anomaly', name), got {source!r}")
+            direction = ev.get("direction", "ge")
+            if direction not in ("ge", "le"):
+                raise ValueError(f"EventTable: event '{label}': direction must be 'ge' or 'le', got {direction!r}")
+            try:
+                t64 = np.asarray(list(ev["thresholds"]), np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError(f"EventTable: event '{label}': thresholds must be a list of numbers") from None
+            if not 1 <= t64.size <= self.tmax:
+                raise ValueError(f"EventTable: event '{label}' has {t64.size} thresholds, 1 to {self.tmax} are allowed")
+            with np.errstate(over="ignore"):
+                t32 = t64.astype(np.float32)
+            if not np.isfinite(t64).all() or not np.isfinite(t32).all():
+                raise ValueError(f"EventTable: event '{label}': thresholds must be finite (in float32)")
+            sign = np.float32(1.0 if direction == "ge" else -1.0)
+            src[s] = (kind, c0, c1, t32.size)
+            thr[s, 0] = sign
+            thr[s, 1:1 + t32.size] = sign * t32
+            self.labels.append(label)
+            self.thresholds.append([float(v) for v in t32])
+            self.directions.append(direction)
+        self.kinds = [int(k) for k in src[:, 0]]
+        self.n_thresholds = [int(n) for n in src[:, 3]]
+        self.T = max(self.n_thresholds)
+        self._src, self._thr = np.ascontiguousarray(src), np.ascontiguousarray(thr)
+        self._bytes_per_cell = float(sum(BYTES_PER_CELL[k] for k in self.kinds))
+
+    def bind(self, W: int) -> None:
+        """states the number of longitudes ahead of the first ``update`` (which otherwise does it); ``valid_fraction``
+        needs it"""
+        if isinstance(W, bool) or int(W) != W or int(W) < 1:
+            raise ValueError(f"EventTable.bind: W must be an integer >= 1, got {W!r}")
+        if self.W is not None and int(W) != self.W:
+            raise ValueError(f"EventTable.bind: the table is bound to {self.W} longitudes already")
+        self.W = int(W)
+
+    def _check(self, lead, forecast, truth, clim_index):
+        """argument checks of ``update``; returns (B, C, H, W)"""
+        if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < self.n_leads:
+            raise ValueError(f"EventTable.update: lead must be an integer in [0, {self.n_leads}), got {lead!r}")
+        C, H = len(self.names), self.H
+        for what, t in (("forecast", forecast), ("truth", truth)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 4:
+                raise ValueError(f"EventTable.update: {what} must be a [B, C, H, W] tensor")
+            if t.dtype != torch.float32:
+                raise ValueError(f"EventTable.update: {what} must be float32, got {t.dtype}")
+        B, Cf, Hf, W = forecast.shape
+        if (Cf, Hf) != (C, H) or W < 1:
+            raise ValueError(f"EventTable.update: forecast is {tuple(forecast.shape)}; the table has {C} channels "
+                             f"and {H} latitudes")
+        if truth.shape != forecast.shape:
+            raise ValueError(f"EventTable.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
+        if self.W is not None and W != self.W:
+            raise ValueError(f"EventTable.update: forecast has {W} longitudes, the table is bound to {self.W}")
+        dense_state(forecast, "forecast", "EventTable.update")
+        dense_state(truth, "truth", "EventTable.update")
+        if self.climatology is None:
+            if clim_index is not None:
+                raise ValueError("EventTable.update: clim_index given, but the table has no climatology")
+        else:
+            if self.climatology.shape[3] != W:
+                raise ValueError(f"EventTable.update: forecast has {W} longitudes, the climatology "
+                                 f"{self.climatology.shape[3]}")
+            if clim_index is None:
+                if self.climatology.shape[0] != 1:
+                    raise ValueError(f"EventTable.update: clim_index is needed to choose among the "
+                                     f"{self.climatology.shape[0]} climatology slots")
+            elif not isinstance(clim_index, torch.Tensor) or clim_index.dtype != torch.int32 or \
+                    tuple(clim_index.shape) != (B,):
+                raise ValueError(f"EventTable.update: clim_index must be an int32 tensor [{B}]")
+        return B, C, H, W
+
+    def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
+               clim_index: Optional[torch.Tensor] = None) -> None:
+        B, C, H, W = self._check(lead, forecast, truth, clim_index)
+        require_hip(forecast, truth)
+        if not self.acc.is_cuda:
+            raise RuntimeError("EventTable.update: the table was made with a CPU device (there is no CPU fallback)")
+        if B == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
+            return
+        if self.W is None:
+            self.bind(W)
+        clim = self.climatology
+        if clim is not None:
+            if clim_index is None:
+                if B not in self._slot0:
+                    with torch.inference_mode(False):
+                        self._slot0[B] = torch.zeros(B, dtype=torch.int32, device=forecast.device)
+                clim_index = self._slot0[B]
+            if not clim_index.is_cuda:
+                raise ValueError("EventTable.update: clim_index must live on the device")
+            clim_index = clim_index.contiguous()         # a column of [B, n_stored] becomes dense; no host wait
+        P, S = H * W, len(self.labels)
+        ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_events_ws_bytes(B, S, H, W)))
+        _lib.call("events_update", self._bytes_per_cell * B * P, dptr(forecast), batch_stride(forecast, C * P),
+                  dptr(truth), batch_stride(truth, C * P), dptr(clim), dptr(clim_index) if clim is not None else None,
+                  clim.shape[0] if clim is not None else 0, self._src.ctypes.data, self._thr.ctypes.data,
+                  dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]), dptr(ws), B, C, S, H, W, stream_ptr())
+
+    def reset(self) -> None:
+        self.acc.zero_()
+        self.n_samples.zero_()
+
+    def counts(self, sync_dist: bool = False) -> dict:
+        # (one tensor: the accumulators and, behind them, the sample counts - one all-reduce, one device read)
+        flat = sum_over_ranks(torch.cat([self.acc.reshape(-1), self.n_samples]), sync_dist).numpy()
+        a = flat[:self.acc.numel()].reshape(tuple(self.acc.shape))
+        T, TM = self.T, self.tmax
+        out = {"valid": a[..., 0].copy(), "forecast_yes": a[..., 1:1 + T].copy(),
+               "observed_yes": a[..., 1 + TM:1 + TM + T].copy(), "both": a[..., 1 + 2 * TM:1 + 2 * TM + T].copy(),
+               "n_samples": flat[self.acc.numel():].copy()}
+        for s, n in enumerate(self.n_thresholds):
+            for k in ("forecast_yes", "observed_yes", "both"):
+                out[k][:, s, :, n:] = -1
+        return out
+
+    def result(self, sync_dist: bool = False) -> dict:
+        cnt = self.counts(sync_dist)
+        wb = self.band_w                                                  # [R, H]
+        nV = cnt["valid"].astype(np.float64)                              # [L, S, H]
+        nF, nO, nFO = (cnt[k].astype(np.float64) for k in ("forecast_yes", "observed_yes", "both"))   # [L, S, H, T]
+        fold = lambda x: np.einsum("rh,lsht->lsrt", wb, x)                # noqa: E731
+        a, b, c = fold(nFO), fold(nF - nFO), fold(nO - nFO)
+        d = fold(nV[..., None] - nF - nO + nFO)
+        res = dict(zip(TABLES, (a, b, c, d)))
+        res.update(scores(a, b, c, d))
+        n = cnt["n_samples"]
+        dead = np.zeros(a.shape, bool)
+        dead[n == 0] = True                                               # leads never updated
+        for s, nt in enumerate(self.n_thresholds):
+            dead[:, s, :, nt:] = True                                     # past a source's own thresholds
+        for k in TABLES + SCORES:
+            res[k] = np.where(dead, np.nan, res[k])
+        seen = n.astype(np.float64)[:, None, None] * float(self.W or 0) * wb.sum(axis=1)[None, None, :]
+        with np.errstate(all="ignore"):
+            vf = np.einsum("rh,lsh->lsr", wb, nV) / np.where(seen > 0, seen, np.nan)
+        res["valid_fraction"] = vf
+        res["count"] = n.copy()
+        res["labels"] = list(self.labels)
+        res["thresholds"] = [list(t) for t in self.thresholds]
+        res["directions"] = list(self.directions)
+        res["bands"] = list(self.bands)
+        return res
+
+    scores = staticmethod(scores)
+
+    @staticmethod
+    def table(result: dict, label: str, band: Optional[str] = None,
+              metrics: Sequence[str] = ("frequency_bias", "csi", "ets", "sedi")) -> str:
+        """plain text, one block per metric: a row per lead, a column per threshold of ``label``"""
+        labels: List[str] = list(result["labels"])
+        bands: List[str] = list(result["bands"])
+        if str(label) not in labels:
+            raise ValueError(f"EventTable.table: event '{label}' is not among the table's labels")
+        band = bands[0] if band is None else str(band)
+        if band not in bands:
+            raise ValueError(f"EventTable.table: band '{band}' is not among the table's bands")
+        for m in metrics:
+            if m not in TABLES + SCORES:
+                raise ValueError(f"EventTable.table: '{m}' is not among {TABLES + SCORES}")
+        s, r = labels.index(str(label)), bands.index(band)
+        thr = result["thresholds"][s]
+        op = ">=" if result["directions"][s] == "ge" else "<="
+        lines = [f"{label} / {band}"]
+        for m in metrics:
+            lines.append(f"{m:<16}{'count':>8}" + "".join(f"{op + format(t, '.4g'):>12}" for t in thr))
+            for lead in range(result[m].shape[0]):
+                vals = "".join(f"{result[m][lead, s, r, j]:>12.4f}" for j in range(len(thr)))
+                lines.append(f"{lead:<16d}{int(result['count'][lead]):>8d}" + vals)
+            lines.append("")
+        return "\n".join(lines[:-1])
