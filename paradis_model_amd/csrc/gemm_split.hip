@@ -2,6 +2,8 @@
 // operands' amax, the weight images (amax_partials_kernel, split_weights*_kernel and their entry points), the forward /
 // data-gradient kernels on a 128 x 128 and a 128 x 256 tile, and the launch of the shared weight-gradient kernel with
 // three and two planes.  gemm.hip calls in through pd_split_* (declared in gemm_common.h).
+#include <cstring>
+#include <type_traits>
 #include "gemm_common.h"
 
 namespace {
@@ -106,6 +108,158 @@ split_weights_f16_kernel(const float* __restrict__ W, int64_t rs, int64_t cs, in
     u32x4* o = out + tile * simg(2) + half * SCH + row;
     o[0] = h; o[2 * SCH] = l;
   }
+}
+
+// ---- the interior-tile epilogue of the fp32-width kernels, one instantiation per option set ---------------------------------
+// gemm_epilogue (gemm_common.h) decides every option at run time and waits for each operand tensor of each group of eight
+// values on its own.  Here the option set EPI is a compile-time bit set (the sets a training step launches: SPLIT_WIDE_EPI
+// below; everything else, ragged tiles included, keeps gemm_epilogue), and per element the operations, their order and
+// their contraction are gemm_epilogue's, so the results are the same bits:
+//   * a wave walks its 64 x 64 block as eight groups (tm, h, tn) of eight rows x 64 lanes; all operand loads of group
+//     g + 1 (map, zmul, res) are issued before the arithmetic and the stores of group g, into the registers the k-loop
+//     has released, and waited for by count (the stores count as well: vmcnt retires in order);
+//   * loads and stores take the saddr form - a scalar row pointer plus ONE 32-bit lane offset ((4 lh ldc + li) x 4 bytes;
+//     the second 32-column tile sits in the instruction's immediate offset) - instead of a 64-bit vector address each;
+//   * bias[m] and sigmoid(gate[m]) are per-row values: lane l of a wave fetches row l of the wave's 64 rows once (one
+//     expf and one division per lane and tile instead of 64), and a pair of groups picks its eight rows with ds_bpermute.
+enum : int { EP_ON = 1, EP_BIAS = 2, EP_MAP = 4, EP_ZOUT = 8, EP_SILU = 16, EP_ZMUL = 32, EP_RES = 64, EP_GATE = 128 };
+
+template <int OFF>
+__device__ __forceinline__ void ep_load(float& x, uint32_t voff, const float* p) {
+  asm volatile("global_load_dword %0, %1, %2 offset:%3" : "=&v"(x) : "v"(voff), "s"(p), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void ep_store(float x, uint32_t voff, float* p) {
+  asm volatile("global_store_dword %0, %1, %2 offset:%3" :: "v"(voff), "v"(x), "s"(p), "n"(OFF) : "memory");
+}
+// at most N younger vector-memory operations outstanding; the registers waited for are INPUTS (see USE_X below)
+template <int N>
+__device__ __forceinline__ void ep_wait(const float (&a)[8]) {
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]),
+               "v"(a[7]) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int N>
+__device__ __forceinline__ void ep_wait(const float (&a)[8], const float (&b)[8]) {
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]),
+               "v"(a[7]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int N>
+__device__ __forceinline__ void ep_wait(float a, float b) {
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a), "v"(b) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ float ep_row(float rowvec, int addr) {      // rowvec of lane addr / 4
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(rowvec)));
+}
+template <class T>
+__device__ __forceinline__ T* ep_uniform(T* p) {      // wave-uniform by construction: pin it to scalar registers
+  const uint64_t a = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
+}
+
+template <int EPI>
+__device__ __forceinline__ void split_epilogue_interior(const GemmArgs& g, f32x16 (&acc)[2][2], int bz, int m0, int n0,
+                                                        int wm, int wn, int li, int lh) {
+  constexpr bool BIAS = EPI & EP_BIAS, MAP = EPI & EP_MAP, ZOUT = EPI & EP_ZOUT, SILU = EPI & EP_SILU, ZMUL = EPI & EP_ZMUL,
+                 RES = EPI & EP_RES, GATE = EPI & EP_GATE;
+  static_assert(!(GATE && !RES) && !(ZMUL && (SILU || ZOUT)), "no such epilogue");
+  // operand tensors of a group, their slots in the load buffers, loads / stores per group
+  constexpr int NT = MAP + ZMUL + RES, I_MAP = 0, I_ZM = MAP, I_RES = MAP + ZMUL;
+  static_assert(NT <= 2, "a third operand tensor needs a third ep_wait");
+  constexpr int L = 8 * NT, S = 8 * (1 + ZOUT);
+  const int wrow = __builtin_amdgcn_readfirstlane(m0 + wm * 64), wcol = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
+  const int64_t ld = g.ldc, tile = (int64_t)wrow * ld + wcol;
+  float* const Cs = ep_uniform(g.C + (int64_t)bz * g.c_bs + tile);
+  float* const zos = ZOUT ? ep_uniform(g.zout + (int64_t)bz * g.zout_bs + tile) : nullptr;
+  const float* const mps = MAP ? ep_uniform(g.map + tile) : nullptr;
+  const float* const zms = ZMUL ? ep_uniform(g.zmul + (int64_t)bz * g.zmul_bs + tile) : nullptr;
+  const float* const rss = RES ? ep_uniform(g.res + (int64_t)bz * g.res_bs + tile) : nullptr;
+  const uint32_t voff = ((uint32_t)(4 * lh) * (uint32_t)ld + (uint32_t)li) * 4u;      // (host: ldc < 2^26)
+  const int radr = 16 * lh;                                   // ds_bpermute address of row 4 lh of the wave's 64
+  // group gi = (tm, h, tn); element q sits in row tm 32 + (q & 3) + 8 (2 h + (q >> 2)) (+ 4 lh) of the wave's block
+  auto rowof = [](int gi, int q) constexpr { return (gi >> 2) * 32 + (q & 3) + 8 * (2 * ((gi >> 1) & 1) + (q >> 2)); };
+
+  float bv = 0.f, gv = 0.f;             // lane l: bias / gate of row wrow + l
+  float buf[2][NT ? NT : 1][8];
+  auto issue = [&](auto G) __attribute__((always_inline)) {
+    constexpr int gi = decltype(G)::value, OFF = (gi & 1) * 128;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int64_t ro = (int64_t)rowof(gi, q) * ld;
+      if constexpr (MAP) ep_load<OFF>(buf[gi & 1][I_MAP][q], voff, mps + ro);
+      if constexpr (ZMUL) ep_load<OFF>(buf[gi & 1][I_ZM][q], voff, zms + ro);
+      if constexpr (RES) ep_load<OFF>(buf[gi & 1][I_RES][q], voff, rss + ro);
+    }
+  };
+  float br[8], gr[8];                   // the rows of the current (tm, h): picked at tn = 0, used by both column tiles
+  if constexpr (BIAS) ep_load<0>(bv, (uint32_t)(32 * lh + li) * 4u, ep_uniform(g.bias + wrow));
+  if constexpr (GATE) ep_load<0>(gv, (uint32_t)(32 * lh + li) * 4u, ep_uniform(g.gate + wrow));
+  if constexpr (NT > 0) issue(std::integral_constant<int, 0>{});
+  __builtin_amdgcn_sched_barrier(0);
+
+  auto group = [&](auto G) __attribute__((always_inline)) {
+    constexpr int gi = decltype(G)::value, tm = gi >> 2, h = (gi >> 1) & 1, tn = gi & 1, OFF = tn * 128, b = gi & 1;
+    if constexpr (NT > 0 && gi < 7) {
+      issue(std::integral_constant<int, gi + 1>{});
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (gi == 0 && (BIAS || GATE)) {
+      ep_wait<NT ? 2 * L : 0>(bv, gv);       // younger: the loads of groups 0 and 1
+      if constexpr (GATE) gv = gate_sigmoid(gv);
+    }
+    if constexpr (tn == 0 && (BIAS || GATE)) {      // eight (sixteen) picks back to back, one counted LDS wait each
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        if constexpr (BIAS) br[q] = ep_row(bv, radr + 4 * rowof(gi, q));
+        if constexpr (GATE) gr[q] = ep_row(gv, radr + 4 * rowof(gi, q));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // younger than this group's loads: the stores of the group before, the loads of the group after
+    constexpr int YOUNGER = (gi < 7 ? L : 0) + (gi > 0 ? S : 0);
+    if constexpr (NT == 1) ep_wait<YOUNGER>(buf[b][0]);
+    if constexpr (NT == 2) ep_wait<YOUNGER>(buf[b][0], buf[b][1]);
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = acc[tm][tn][8 * h + q];
+    if constexpr (BIAS) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] += br[q];
+    }
+    if constexpr (MAP) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] += buf[b][I_MAP][q];
+    }
+    if constexpr (ZOUT) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) ep_store<OFF>(v[q], voff, zos + (int64_t)rowof(gi, q) * ld);
+    }
+    if constexpr (ZMUL) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] *= act_grad(buf[b][I_ZM][q], PARADIS_ACT_SILU);
+    } else if constexpr (SILU) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = act_apply(v[q], PARADIS_ACT_SILU);
+    }
+    if constexpr (RES) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float r = buf[b][I_RES][q];
+        if constexpr (GATE) v[q] = fmaf(gr[q], v[q] - r, r);
+        else v[q] += r;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) ep_store<OFF>(v[q], voff, Cs + (int64_t)rowof(gi, q) * ld);
+    __builtin_amdgcn_sched_barrier(0);      // (a group's arithmetic stays behind the stores of the group before)
+  };
+  group(std::integral_constant<int, 0>{}); group(std::integral_constant<int, 1>{});
+  group(std::integral_constant<int, 2>{}); group(std::integral_constant<int, 3>{});
+  group(std::integral_constant<int, 4>{}); group(std::integral_constant<int, 5>{});
+  group(std::integral_constant<int, 6>{}); group(std::integral_constant<int, 7>{});
 }
 
 // fwd / dgrad:  C_b = epi( A . B_b ),  A = split weight image (g.A, batch stride g.a_bs chunks),
@@ -279,7 +433,9 @@ pw_gemm_split_kernel(GemmArgs g) {
 #ifndef SPLIT_STAGGER         // (-DSPLIT_STAGGER=1: A/B build of the staggered 128 x 256 kernel)
 #define SPLIT_STAGGER 0
 #endif
-template <int NSUB, int NP = 2>
+// EPI: 0 = gemm_epilogue for every tile; an option set (EP_ON | ...) = split_epilogue_interior<EPI> for the interior tiles of
+// a launch whose options ARE that set (the host's choice: split_epilogue_flags), gemm_epilogue for its ragged tiles.
+template <int NSUB, int NP = 2, int EPI = 0>
 __global__ void __launch_bounds__(256 * NSUB, 4)      // (second argument: waves per SIMD)
 pw_gemm_split_wide_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -457,9 +613,22 @@ pw_gemm_split_wide_kernel(GemmArgs g) {
   }
 #undef USE_X
   if (live) {
-    split_unflip(acc, wn);
-    if constexpr (NP == 2) split_unscale(acc, inv_a, inv_b);
-    gemm_epilogue(g, acc, bz, m0, n0, wm, wn, li, lh);
+    if constexpr (EPI != 0) {
+      // The epilogue's lane values are derived afresh from ONE register (the thread index, opaque to the compiler from
+      // here on): values of theirs that the compiler computes ahead of the k-loop stay live through it, and one register
+      // more at the 128 this kernel has turns the k-loop's schedule into a pressure-driven one.
+      int t = tid;
+      asm volatile("" : "+v"(t));
+      const int ew = __builtin_amdgcn_readfirstlane((t >> 6) & 3), ewm = ew >> 1, ewn = ew & 1, eli = t & 31, elh = (t >> 5) & 1;
+      split_unflip(acc, ewn);
+      if constexpr (NP == 2) split_unscale(acc, inv_a, inv_b);
+      if (m0 + BM <= g.M && n0 + BN <= g.N) split_epilogue_interior<EPI>(g, acc, bz, m0, n0, ewm, ewn, eli, elh);
+      else gemm_epilogue(g, acc, bz, m0, n0, ewm, ewn, eli, elh);
+    } else {
+      split_unflip(acc, wn);
+      if constexpr (NP == 2) split_unscale(acc, inv_a, inv_b);
+      gemm_epilogue(g, acc, bz, m0, n0, wm, wn, li, lh);
+    }
   }
 }
 
@@ -509,6 +678,32 @@ constexpr GemmKernelEntry SPLIT_WIDE[2] = {{&pw_gemm_split_wide_kernel<SPLIT_WID
                                            {&pw_gemm_split_wide_kernel<SPLIT_WIDE_NSUB, 3>, split_wide_lds(SPLIT_WIDE_NSUB, 3)}};
 constexpr GemmKernelEntry SPLIT_WGRAD[2] = {{&pw_gemm_wgrad_split_kernel<2>, split_lds_wgrad(2)},
                                             {&pw_gemm_wgrad_split_kernel<3>, split_lds_wgrad(3)}};
+// bf16x3 on the 128 x 256 tile with a compile-time epilogue: the option sets the default model's training step launches
+// (DESIGN.md 4.1), SPLIT_WIDE_EPI_SETS[i] = the set of SPLIT_WIDE_EPI[i].  Any other set runs SPLIT_WIDE.
+#define EPI_SETS(X)                                                                                                       \
+  X(EP_ON) X(EP_ON | EP_ZMUL)                                                              /* data gradient */           \
+  X(EP_ON | EP_BIAS) X(EP_ON | EP_BIAS | EP_RES) X(EP_ON | EP_BIAS | EP_RES | EP_GATE)     /* forward */                 \
+  X(EP_ON | EP_BIAS | EP_SILU | EP_ZOUT) X(EP_ON | EP_BIAS | EP_MAP | EP_RES)                                            \
+  X(EP_ON | EP_BIAS | EP_MAP | EP_SILU | EP_ZOUT)
+#define EPI_SET(E) (E),
+#define EPI_ENTRY(E) {&pw_gemm_split_wide_kernel<SPLIT_WIDE_NSUB, 3, (E)>, split_wide_lds(SPLIT_WIDE_NSUB, 3)},
+constexpr int SPLIT_WIDE_EPI_SETS[] = {EPI_SETS(EPI_SET)};
+constexpr GemmKernelEntry SPLIT_WIDE_EPI[] = {EPI_SETS(EPI_ENTRY)};
+#undef EPI_ENTRY
+#undef EPI_SET
+#undef EPI_SETS
+
+// the option set of a launch as split_epilogue_interior spells it; 0: a set it does not cover (the projected GlobalBias,
+// GELU, an activation gradient without an activation, a lane offset beyond 32 bits).  PARADIS_GEMM_EPILOGUE=generic
+// (read at every launch: an A/B, or a test of one path against the other, needs one process) answers 0 for every launch.
+int split_epilogue_flags(const GemmArgs& d) {
+  const char* e = getenv("PARADIS_GEMM_EPILOGUE");
+  if (e && strcmp(e, "generic") == 0) return 0;
+  if (d.pw || d.io16 || d.ldc >= (1 << 26) || (d.gate && !d.res)) return 0;
+  if (d.zmul ? d.act != PARADIS_ACT_SILU : (d.act != 0 && d.act != PARADIS_ACT_SILU)) return 0;
+  return EP_ON | (d.bias ? EP_BIAS : 0) | (d.map ? EP_MAP : 0) | (d.zout ? EP_ZOUT : 0) | (d.zmul ? EP_ZMUL : 0) |
+         (!d.zmul && d.act ? EP_SILU : 0) | (d.res ? EP_RES : 0) | (d.gate ? EP_GATE : 0);
+}
 
 }  // namespace
 
@@ -587,9 +782,17 @@ extern "C" int paradis_pw_gemm_split_weights_pair(const float* W, int M, int K, 
 
 // ---- what gemm.hip calls --------------------------------------------------------------------------------------------------
 int pd_split_launch(const GemmArgs& d, int scheme, hipStream_t st) {
-  static PerDeviceOnce once, once_wide;
+  static PerDeviceOnce once, once_wide, once_epi;
   const int np = scheme == PARADIS_GEMM_F16X2 ? 2 : 3;
   const int MT = (d.M + BM - 1) / BM, NT = (d.N + BN - 1) / BN;
+  if (NT >= 2 && np == 3 && SPLIT_WIDE_BF16X3) {      // ... with the launch's option set compiled in, where one is built
+    constexpr int NE = sizeof(SPLIT_WIDE_EPI_SETS) / sizeof(int);
+    const int set = split_epilogue_flags(d);
+    for (int i = 0; set != 0 && i < NE; ++i)
+      if (SPLIT_WIDE_EPI_SETS[i] == set)
+        return launch_entry(SPLIT_WIDE_EPI, i, once_epi, "pw_gemm(split)", MT * ((NT + SPLIT_WIDE_NSUB - 1) / SPLIT_WIDE_NSUB) * d.nbatch,
+                            256 * SPLIT_WIDE_NSUB, st, d);
+  }
   if (NT >= 2 && (np == 2 || SPLIT_WIDE_BF16X3))      // 128 x (128 NSUB) tiles
     return launch_entry(SPLIT_WIDE, np - 2, once_wide, "pw_gemm(split)", MT * ((NT + SPLIT_WIDE_NSUB - 1) / SPLIT_WIDE_NSUB) * d.nbatch,
                         256 * SPLIT_WIDE_NSUB, st, d);
