@@ -773,6 +773,41 @@ int paradis_events_update(const float* fc, int64_t fc_bs, const float* truth, in
                           int64_t* acc_lead, int64_t* n_samples_lead, void* ws, int B, int C, int S, int H, int W,
                           void* stream);
 
+/* ---- Neighbourhood verification (ABI 10, additive), csrc/fss.hip: the integer sums of the fractions skill score per
+ * lead, event source, latitude row, scale and threshold.  Three launches on `stream` (the decision and the row counts;
+ * the windows; the finish), no host synchronisation, no memset or copy nodes, no atomics, no float arithmetic after the
+ * decision: the sums are exact.
+ *   fc, truth, fc_bs, truth_bs, clim, clim_index, K_clim, src_table, thr_table: as paradis_events_update (K there),
+ *   with its limits (paradis_events_max_sources(), paradis_events_max_thresholds() = TMAX) and its checks; the decided
+ *   bits F[j], O[j] are those of events.hip, and an INVALID CELL IS A NON-EVENT in both fields;
+ *   half_y HOST int32 [K]: the latitude half-width ny[k] of scale k in rows, 0 .. paradis_fss_max_half_y() (read on the
+ *   host, travels as a kernel argument); K in 1 .. paradis_fss_max_scales() (K_MAX);
+ *   half_x DEVICE int32 [K][H]: the longitude half-width nx[k][h] of the windows centred in row h, in cells.  It cannot
+ *   be checked on the host: THE KERNEL CLAMPS every entry into [0, min(paradis_fss_max_half_x(), (W - 1) / 2)].
+ * The window of centre cell (h, w) at scale k: rows max(0, h - ny) .. min(H - 1, h + ny) (clipped at the grid edge, no
+ * over-the-pole wrap), columns w - nx .. w + nx modulo W; cF / cO: the F / O bits in it.
+ *   acc_lead: DEVICE int64 [S][H][1 + 2 TMAX + 3 K_MAX TMAX], the row of this lead:
+ *     [0] nV   [1 + j] nF[j]   [1 + TMAX + j] nO[j]                              (paradis_events_update's counts)
+ *     [1 + 2 TMAX + 3 (k TMAX + j) + q]   q = 0: sum_w cF^2, 1: sum_w cO^2, 2: sum_w cF cO
+ *   each += the sums of this call (entries past nthr or K: += 0 or untouched); n_samples_lead: DEVICE int64 [1] += B.
+ * ws: paradis_fss_ws_bytes(B, S, H, W, K) bytes, 16-byte aligned: the decided bits uint16 [B][S][H][W], then uint64
+ * partials [B][S][H][1 + 2 TMAX + 3 K TMAX].  A workgroup of the window kernel owns paradis_fss_rows(W, ny_max) centre
+ * rows of one (sample, source, scale) (0 for a W or ny_max outside the limits) and reads 2 ny[k] halo rows of bits.
+ * B == 0 does nothing.  rc 1 before any HIP call for everything paradis_events_update refuses, W above
+ * paradis_fss_max_w(), K outside [1, K_MAX], a half_y entry outside its range, a NULL table, half_y or half_x, a ws that
+ * is not 16-byte aligned.  W % 4 == 0 with 16-byte aligned bases and strides takes 16-byte loads, anything else scalar
+ * loads: the same integers.  Algorithmic HBM bytes per cell of a source: 8 plain, 16 speed, 12 anomaly. */
+int paradis_fss_max_scales(void);
+int paradis_fss_max_half_y(void);
+int paradis_fss_max_half_x(void);
+int paradis_fss_max_w(void);
+int paradis_fss_rows(int W, int ny_max);
+size_t paradis_fss_ws_bytes(int B, int S, int H, int W, int K);
+int paradis_fss_update(const float* fc, int64_t fc_bs, const float* truth, int64_t truth_bs, const float* clim,
+                       const int* clim_index, int K_clim, const int* src_table, const float* thr_table,
+                       const int* half_y, const int* half_x, int64_t* acc_lead, int64_t* n_samples_lead, void* ws,
+                       int B, int C, int S, int H, int W, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

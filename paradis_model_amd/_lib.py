@@ -149,6 +149,13 @@ SIGNATURES = {
     "paradis_events_rows": (I, [I]),
     "paradis_events_ws_bytes": (S, [I, I, I, I]),
     "paradis_events_update": (I, [P, L, P, L, P, P, I, P, P, P, P, P, I, I, I, I, I, P]),
+    "paradis_fss_max_scales": (I, []),
+    "paradis_fss_max_half_y": (I, []),
+    "paradis_fss_max_half_x": (I, []),
+    "paradis_fss_max_w": (I, []),
+    "paradis_fss_rows": (I, [I, I]),
+    "paradis_fss_ws_bytes": (S, [I, I, I, I, I]),
+    "paradis_fss_update": (I, [P, L, P, L, P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
 }
 
 _missing = []

@@ -92,6 +92,77 @@ def scores(a, b, c, d) -> dict:
                 "sedi": _ratio(lf - lh - l1f + l1h, lf + lh + l1f + l1h)}
 
 
+def parse_events(who: str, events, names: Sequence[str], with_climatology: bool) -> dict:
+    """the ``events`` dict of ``EventTable`` (and ``neighbourhood.FractionsTable``) checked and turned into the attributes
+    both keep: ``tmax``, ``labels``, ``thresholds``, ``directions``, ``kinds``, ``n_thresholds``, ``T`` and the two host
+    tables of the entry points, ``_src`` int32 ``[S, 4]`` and ``_thr`` float32 ``[S, 1 + tmax]``, and
+    ``_bytes_per_cell``.  ``who`` opens every message."""
+    names = list(names)
+
+    def channel(label, name) -> int:
+        if not isinstance(name, str) or name not in names:
+            raise ValueError(f"{who}: event '{label}': channel {name!r} is not among the names")
+        return names.index(name)
+
+    tmax = max_thresholds()
+    smax = int(_lib.lib.paradis_events_max_sources())
+    if not isinstance(events, dict) or len(events) < 1:
+        raise ValueError(f"{who}: events must be a non-empty dict label -> {{source, thresholds, direction}}")
+    if len(events) > smax:
+        raise ValueError(f"{who}: {len(events)} events, at most {smax} go into one table")
+    labels: List[str] = []
+    thresholds: List[List[float]] = []
+    directions: List[str] = []
+    src = np.zeros((len(events), 4), np.int32)
+    thr = np.zeros((len(events), 1 + tmax), np.float32)
+    for s, (label, ev) in enumerate(events.items()):
+        label = str(label)
+        if not isinstance(ev, dict) or "source" not in ev or "thresholds" not in ev or \
+                set(ev) - {"source", "thresholds", "direction"}:
+            raise ValueError(f"{who}: event '{label}' must be a dict with source, thresholds and, optionally, "
+                             f"direction")
+        source = ev["source"]
+        if isinstance(source, str):
+            kind, c0, c1 = KINDS["plain"], channel(label, source), 0
+        elif isinstance(source, (tuple, list)) and len(source) == 3 and source[0] == "speed":
+            kind, c0, c1 = KINDS["speed"], channel(label, source[1]), channel(label, source[2])
+            if c0 == c1:
+                raise ValueError(f"{who}: event '{label}': the speed of '{source[1]}' with itself is refused "
+                                 f"(take the plain channel with both directions instead)")
+        elif isinstance(source, (tuple, list)) and len(source) == 2 and source[0] == "anomaly":
+            kind, c0, c1 = KINDS["anomaly"], channel(label, source[1]), 0
+            if not with_climatology:
+                raise ValueError(f"{who}: event '{label}' is an anomaly, but the table has no climatology")
+        else:
+            raise ValueError(f"{who}: event '{label}': source must be 'name', ('speed', a, b) or "
+                             f"('anomaly', name), got {source!r}")
+        direction = ev.get("direction", "ge")
+        if direction not in ("ge", "le"):
+            raise ValueError(f"{who}: event '{label}': direction must be 'ge' or 'le', got {direction!r}")
+        try:
+            t64 = np.asarray(list(ev["thresholds"]), np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: event '{label}': thresholds must be a list of numbers") from None
+        if not 1 <= t64.size <= tmax:
+            raise ValueError(f"{who}: event '{label}' has {t64.size} thresholds, 1 to {tmax} are allowed")
+        with np.errstate(over="ignore"):
+            t32 = t64.astype(np.float32)
+        if not np.isfinite(t64).all() or not np.isfinite(t32).all():
+            raise ValueError(f"{who}: event '{label}': thresholds must be finite (in float32)")
+        sign = np.float32(1.0 if direction == "ge" else -1.0)
+        src[s] = (kind, c0, c1, t32.size)
+        thr[s, 0] = sign
+        thr[s, 1:1 + t32.size] = sign * t32
+        labels.append(label)
+        thresholds.append([float(v) for v in t32])
+        directions.append(direction)
+    kinds = [int(k) for k in src[:, 0]]
+    n_thresholds = [int(n) for n in src[:, 3]]
+    return {"tmax": tmax, "labels": labels, "thresholds": thresholds, "directions": directions, "kinds": kinds,
+            "n_thresholds": n_thresholds, "T": max(n_thresholds), "_src": np.ascontiguousarray(src),
+            "_thr": np.ascontiguousarray(thr), "_bytes_per_cell": float(sum(BYTES_PER_CELL[k] for k in kinds))}
+
+
 class EventTable:
     """Per-lead contingency tables of threshold events, accumulated on the device (module docstring for the definitions;
     invalid - non-finite - cells are counted in no class, unlike ``Scorecard``, where NaN propagates).
@@ -173,70 +244,10 @@ class EventTable:
         self._ws: Dict[tuple, torch.Tensor] = {}      # (device, stream) -> workspace
         self._slot0: Dict[int, torch.Tensor] = {}     # B -> zeros [B] int32: the index of a one-slot climatology
 
-    def _channel(self, label, name) -> int:
-        if not isinstance(name, str) or name not in self.names:
-            raise ValueError(f"EventTable: event '{label}': channel {name!r} is not among the names")
-        return self.names.index(name)
-
     def _parse(self, events) -> None:
         """labels, kinds, thresholds, directions and the two host tables of the entry point"""
-        self.tmax = max_thresholds()
-        smax = int(_lib.lib.paradis_events_max_sources())
-        if not isinstance(events, dict) or len(events) < 1:
-            raise ValueError("EventTable: events must be a non-empty dict label -> {source, thresholds, direction}")
-        if len(events) > smax:
-            raise ValueError(f"EventTable: {len(events)} events, at most {smax} go into one table")
-        self.labels: List[str] = []
-        self.thresholds: List[List[float]] = []
-        self.directions: List[str] = []
-        src = np.zeros((len(events), 4), np.int32)
-        thr = np.zeros((len(events), 1 + self.tmax), np.float32)
-        for s, (label, ev) in enumerate(events.items()):
-            label = str(label)
-            if not isinstance(ev, dict) or "source" not in ev or "thresholds" not in ev or \
-                    set(ev) - {"source", "thresholds", "direction"}:
-                raise ValueError(f"EventTable: event '{label}' must be a dict with source, thresholds and, optionally, "
-                                 f"direction")
-            source = ev["source"]
-            if isinstance(source, str):
-                kind, c0, c1 = KINDS["plain"], self._channel(label, source), 0
-            elif isinstance(source, (tuple, list)) and len(source) == 3 and source[0] == "speed":
-                kind, c0, c1 = KINDS["speed"], self._channel(label, source[1]), self._channel(label, source[2])
-                if c0 == c1:
-                    raise ValueError(f"EventTable: event '{label}': the speed of '{source[1]}' with itself is refused "
-                                     f"(take the plain channel with both directions instead)")
-            elif isinstance(source, (tuple, list)) and len(source) == 2 and source[0] == "anomaly":
-                kind, c0, c1 = KINDS["anomaly"], self._channel(label, source[1]), 0
-                if self.climatology is None:
-                    raise ValueError(f"EventTable: event '{label}' is an anomaly, but the table has no climatology")
-            else:
-                raise ValueError(f"EventTable: event '{label}': source must be 'name', ('speed', a, b) or "
-                                 f"('anomaly', name), got {source!r}")
-            direction = ev.get("direction", "ge")
-            if direction not in ("ge", "le"):
-                raise ValueError(f"EventTable: event '{label}': direction must be 'ge' or 'le', got {direction!r}")
-            try:
-                t64 = np.asarray(list(ev["thresholds"]), np.float64).reshape(-1)
-            except (TypeError, ValueError):
-                raise ValueError(f"EventTable: event '{label}': thresholds must be a list of numbers") from None
-            if not 1 <= t64.size <= self.tmax:
-                raise ValueError(f"EventTable: event '{label}' has {t64.size} thresholds, 1 to {self.tmax} are allowed")
-            with np.errstate(over="ignore"):
-                t32 = t64.astype(np.float32)
-            if not np.isfinite(t64).all() or not np.isfinite(t32).all():
-                raise ValueError(f"EventTable: event '{label}': thresholds must be finite (in float32)")
-            sign = np.float32(1.0 if direction == "ge" else -1.0)
-            src[s] = (kind, c0, c1, t32.size)
-            thr[s, 0] = sign
-            thr[s, 1:1 + t32.size] = sign * t32
-            self.labels.append(label)
-            self.thresholds.append([float(v) for v in t32])
-            self.directions.append(direction)
-        self.kinds = [int(k) for k in src[:, 0]]
-        self.n_thresholds = [int(n) for n in src[:, 3]]
-        self.T = max(self.n_thresholds)
-        self._src, self._thr = np.ascontiguousarray(src), np.ascontiguousarray(thr)
-        self._bytes_per_cell = float(sum(BYTES_PER_CELL[k] for k in self.kinds))
+        for k, v in parse_events("EventTable", events, self.names, self.climatology is not None).items():
+            setattr(self, k, v)
 
     def bind(self, W: int) -> None:
         """states the number of longitudes ahead of the first ``update`` (which otherwise does it); ``valid_fraction``

@@ -239,6 +239,11 @@ class Forecaster:
     ``events.update`` at lead ``k`` (one more launch pair on the main stream, right after the others and in front of
     the same event).  The refusals are the scorecard's.
 
+    ``run(..., fractions=<neighbourhood.FractionsTable>, truth=..., truth_normalized=False, clim_index=...)``: beside or
+    without the others, the same finished state, truth state and ``clim_index`` column go through ``fractions.update``
+    at lead ``k`` (three more launches on the main stream, right after the others and in front of the same event).
+    The refusals are the event table's.
+
     ``run(..., encoder=<encode.EncodeSpec>, init=<(state [B, 1, C, H, W], dew [B, 1, L, H, W] or None) or None>)``: a
     flushed chunk is regrouped into the writer's named variables and BitRounded on the device (``encode.encode_chunk``,
     one launch on the main stream) into a ring of its own, which is handed over in place of the plain chunk, with the
@@ -272,14 +277,15 @@ class Forecaster:
         return ring.pin() if pinned else ring
 
     def _check_verification(self, scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W, spectra=None,
-                            events=None):
-        """the refusals of ``run(scorecard=..., spectra=..., events=...)``, before the rollout starts; returns the
-        forecaster's ``[B, 1, C, H, W]`` scratch tensor for a model-space truth (``truth_normalized=True``), else None"""
-        if scorecard is None and spectra is None and events is None:
+                            events=None, fractions=None):
+        """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=...)``, before the rollout starts;
+        returns the forecaster's ``[B, 1, C, H, W]`` scratch tensor for a model-space truth (``truth_normalized=True``),
+        else None"""
+        if scorecard is None and spectra is None and events is None and fractions is None:
             if truth is not None or clim_index is not None or truth_normalized:
                 raise ValueError("Forecaster.run: truth, truth_normalized and clim_index go with a scorecard")
             return None
-        if scorecard is None and events is None and clim_index is not None:
+        if scorecard is None and events is None and fractions is None and clim_index is not None:
             raise ValueError("Forecaster.run: clim_index goes with a scorecard")
         if truth.dim() != 5 or tuple(truth.shape) != (B, n_stored, C, H, W) or truth.dtype != torch.float32:
             raise ValueError(f"Forecaster.run: truth must be float32 {(B, n_stored, C, H, W)} (n_stored = {n_stored} "
@@ -296,6 +302,12 @@ class Forecaster:
             raise ValueError(f"Forecaster.run: the event table has {events.n_leads} leads, the rollout stores {n_stored}")
         if events is not None and list(events.names) != list(self.spec.names):
             raise ValueError("Forecaster.run: the event table's names are not the chunk's channel names (PostSpec.names)")
+        if fractions is not None and fractions.n_leads < n_stored:
+            raise ValueError(f"Forecaster.run: the fractions table has {fractions.n_leads} leads, the rollout stores "
+                             f"{n_stored}")
+        if fractions is not None and list(fractions.names) != list(self.spec.names):
+            raise ValueError("Forecaster.run: the fractions table's names are not the chunk's channel names "
+                             "(PostSpec.names)")
         if clim_index is not None and (clim_index.dtype != torch.int32 or tuple(clim_index.shape) != (B, n_stored)):
             raise ValueError(f"Forecaster.run: clim_index must be int32 {(B, n_stored)}, got {clim_index.dtype} "
                              f"{tuple(clim_index.shape)}")
@@ -336,13 +348,15 @@ class Forecaster:
     def run(self, input_data, forcings, constants, on_chunk: Optional[Callable],
             forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
             truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None, encoder=None, init=None,
-            spectra=None, events=None):
+            spectra=None, events=None, fractions=None):
         if scorecard is not None and truth is None:          # (a host-side refusal, in front of the device checks)
             raise ValueError("Forecaster.run: a scorecard needs truth [B, n_stored, C, H, W] on the device")
         if spectra is not None and truth is None:
             raise ValueError("Forecaster.run: spectra need truth [B, n_stored, C, H, W] on the device")
         if events is not None and truth is None:
             raise ValueError("Forecaster.run: an event table needs truth [B, n_stored, C, H, W] on the device")
+        if fractions is not None and truth is None:
+            raise ValueError("Forecaster.run: a fractions table needs truth [B, n_stored, C, H, W] on the device")
         require_hip(input_data, forcings, constants)
         S = int(forcings.shape[1] if forecast_steps is None else forecast_steps)
         if forcings.shape[1] < S:
@@ -352,7 +366,7 @@ class Forecaster:
         B, _, _, H, W = input_data.shape
         C, L = self.spec.num_channels, self.spec.num_levels
         truth_phys = self._check_verification(scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W,
-                                              spectra, events)
+                                              spectra, events, fractions)
         init = self._check_encoder(encoder, init, B, C, L, H, W)
         sizes = [p.flush[1] for p in plan if p.flush is not None]         # per chunk its number of states
         n_chunk, sizes = max(sizes), iter(sizes)
@@ -381,7 +395,7 @@ class Forecaster:
                     views = chunks.open(next(sizes))
                     d, dd = views["state"], views.get("dew")
                 postprocess(out, self.spec, self.lat_deg, self.lon_deg, d, p.slot, dd)
-                if scorecard is not None or spectra is not None or events is not None:
+                if scorecard is not None or spectra is not None or events is not None or fractions is not None:
                     t = truth[:, i_stored]
                     if truth_phys is not None:             # a model-space truth: to physical units first
                         postprocess(t, self.spec, self.lat_deg, self.lon_deg, truth_phys, 0)
@@ -394,6 +408,9 @@ class Forecaster:
                     if events is not None:
                         events.update(i_stored, d[:, p.slot], t,
                                       None if clim_index is None else clim_index[:, i_stored])
+                    if fractions is not None:
+                        fractions.update(i_stored, d[:, p.slot], t,
+                                         None if clim_index is None else clim_index[:, i_stored])
                 i_stored += 1
             if p.flush is not None:
                 start, n = p.flush
