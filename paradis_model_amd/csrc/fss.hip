@@ -35,8 +35,7 @@
 
 namespace {
 
-constexpr int FSS_TMAX = 8;                        // thresholds per source (events.hip's)
-constexpr int FSS_SMAX = 16;                       // sources per launch (events.hip's)
+constexpr int FSS_TMAX = EVSRC_TMAX;
 constexpr int FSS_KMAX = 8;                        // scales per launch
 constexpr int FSS_MAX_HY = 16;                     // latitude half-width, rows
 constexpr int FSS_MAX_HX = 64;                     // longitude half-width, cells
@@ -53,34 +52,17 @@ static_assert(16ull * FSS_NC * ((2 * FSS_MAX_HY + 1) * (2 * FSS_MAX_HX + 1)) * (
 // centre rows per workgroup of the window kernel: few, so that one 721x1440 state gives every CU several workgroups
 // of every scale (the halo is two-byte bits out of L2, cheap beside the window sums)
 inline int fss_rows() { return 8; }
-inline int decide_rows(int W) { return W >= PLANE_PIECE ? 1 : PLANE_PIECE / (W < 1 ? 1 : W); }
 inline size_t mask_bytes(int B, int S, int H, int W) {
   return ((size_t)B * S * H * W * sizeof(uint16_t) + 15) / 16 * 16;
 }
 inline int row_counters(int K) { return FSS_HEAD + 3 * K * FSS_TMAX; }
 
-__device__ __forceinline__ unsigned count_lanes(bool p) { return (unsigned)__popcll(__ballot(p)); }
-
 // ---------------------------------------------------------------------------------------------- 1. the decision
 struct DecideArgs {
-  const float* fc;
-  const float* truth;
-  const float* clim;        // [K][C][P] or null
-  const int* clim_index;    // [B] or null
+  SourceInputs in;
   uint16_t* mask;           // [B][S][H][W]
   unsigned long long* partial;   // [B][S][H][n_row]
-  int64_t fc_bs, truth_bs, P;
-  int C, S, H, W, K_clim, rows, ngroups, n_row;
-  int src[FSS_SMAX][4];                // {kind, c0, c1, nthr}, checked on the host
-  float thr[FSS_SMAX][1 + FSS_TMAX];   // {sign, thr'...}
-};
-
-struct SourcePlanes {
-  const float* f0;
-  const float* t0;
-  const float* f1;
-  const float* t1;
-  const float* cl;
+  int n_row;
 };
 
 // rows h0 + wave, h0 + wave + 4, .. < h1 of one (sample, source)
@@ -90,10 +72,8 @@ __device__ __forceinline__ void decide_rows_of_wave(const SourcePlanes& p, const
                                                     unsigned long long* __restrict__ out, int n_row) {
   const int lane = (int)(threadIdx.x & 63);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const float sign = tab[0];
   float th[FSS_TMAX];
-#pragma unroll
-  for (int j = 0; j < FSS_TMAX; ++j) th[j] = j < nthr ? tab[1 + j] : NAN;       // (x >= NaN is never an event)
+  const float sign = source_thresholds(tab, nthr, th);
   const int wpr = (W + 255) / 256;                                              // walks per row
   for (int h = h0 + wave; h < h1; h += 4) {
     const int64_t row = (int64_t)h * W;
@@ -102,6 +82,8 @@ __device__ __forceinline__ void decide_rows_of_wave(const SourcePlanes& p, const
     for (int j = 0; j < FSS_TMAX; ++j) nF[j] = nO[j] = 0;
 #pragma clang loop vectorize(disable) interleave(disable)
     for (int wk = 0; wk < wpr; ++wk) {
+      // (source_load_walk's loads spelt out into local arrays: with the quads in a SourceQuads this loop's schedule came
+      // out 6-7 % slower for speed sources)
       const int w0 = 256 * wk + 4 * lane;
       const int at = VEC ? min(w0, W - 4) : w0;           // (VEC: W % 4 == 0, a lane past the end reloads the last quad)
       float fa[4], ta[4], fb[4], tb[4], cv[4];
@@ -118,10 +100,7 @@ __device__ __forceinline__ void decide_rows_of_wave(const SourcePlanes& p, const
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float sf, st;
-        bool ok = (VEC ? w0 : w0 + k) < W;
-        ok = event_source_value<KIND>(fa[k], fb[k], cv[k], sign, sf) && ok;
-        ok = event_source_value<KIND>(ta[k], tb[k], cv[k], sign, st) && ok;
-        if (KIND == EVSRC_ANOMALY) ok = ok && __builtin_isfinite(cv[k]);
+        const bool ok = event_cell<KIND>((VEC ? w0 : w0 + k) < W, fa[k], ta[k], fb[k], tb[k], cv[k], sign, sf, st);
         nV += count_lanes(ok);
         unsigned bits = 0;
 #pragma unroll
@@ -153,35 +132,31 @@ __device__ __forceinline__ void decide_rows_of_wave(const SourcePlanes& p, const
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) fss_decide_kernel(DecideArgs a) {
-  const int64_t pair = blockIdx.x / a.ngroups;                       // b S + s
-  const int g = (int)(blockIdx.x - pair * a.ngroups);
-  const int b = (int)(pair / a.S), s = (int)(pair - (int64_t)b * a.S);
-  const int kind = a.src[s][0], c0 = a.src[s][1], c1 = a.src[s][2], nthr = a.src[s][3];
-  const int h0 = g * a.rows, h1 = min(a.H, h0 + a.rows);
-  unsigned long long* out = a.partial + pair * a.H * a.n_row;
-  uint16_t* mask = a.mask + pair * a.P;
-  SourcePlanes p;
-  p.f0 = a.fc + (int64_t)b * a.fc_bs + (int64_t)c0 * a.P;
-  p.t0 = a.truth + (int64_t)b * a.truth_bs + (int64_t)c0 * a.P;
-  p.f1 = a.fc + (int64_t)b * a.fc_bs + (int64_t)c1 * a.P;
-  p.t1 = a.truth + (int64_t)b * a.truth_bs + (int64_t)c1 * a.P;
-  p.cl = nullptr;
-  const float* tab = a.thr[s];
+  const SourceInputs& in = a.in;
+  const int64_t pair = blockIdx.x / in.ngroups;                      // b S + s
+  const int g = (int)(blockIdx.x - pair * in.ngroups);
+  const int b = (int)(pair / in.S), s = (int)(pair - (int64_t)b * in.S);
+  const int kind = in.src[s][0], nthr = in.src[s][3];
+  const int h0 = g * in.rows, h1 = min(in.H, h0 + in.rows);
+  unsigned long long* out = a.partial + pair * in.H * a.n_row;
+  uint16_t* mask = a.mask + pair * in.P;
+  SourcePlanes p = source_planes(in, b, s);
+  const float* tab = in.thr[s];
   if (kind == EVSRC_ANOMALY) {
-    const int k = a.clim_index[b];
-    if (k < 0 || k >= a.K_clim) {                  // (workgroup-uniform) no valid cell; nothing of such a slot is read
-      for (int64_t i = (int64_t)h0 * a.W + threadIdx.x; i < (int64_t)h1 * a.W; i += 256) mask[i] = 0;
+    const int slot = in.clim_index[b];
+    if (slot < 0 || slot >= in.K) {                  // (workgroup-uniform) no valid cell; nothing of such a slot is read
+      for (int64_t i = (int64_t)h0 * in.W + threadIdx.x; i < (int64_t)h1 * in.W; i += 256) mask[i] = 0;
       const int lane = (int)(threadIdx.x & 63);
       for (int h = h0 + (int)(threadIdx.x >> 6); h < h1; h += 4)
         if (lane < FSS_HEAD) out[(int64_t)h * a.n_row + lane] = 0ull;
       return;
     }
-    p.cl = a.clim + ((int64_t)k * a.C + c0) * a.P;
-    decide_rows_of_wave<EVSRC_ANOMALY, VEC>(p, tab, nthr, a.W, h0, h1, mask, out, a.n_row);
+    p.cl = in.clim + ((int64_t)slot * in.C + in.src[s][1]) * in.P;
+    decide_rows_of_wave<EVSRC_ANOMALY, VEC>(p, tab, nthr, in.W, h0, h1, mask, out, a.n_row);
   } else if (kind == EVSRC_SPEED) {
-    decide_rows_of_wave<EVSRC_SPEED, VEC>(p, tab, nthr, a.W, h0, h1, mask, out, a.n_row);
+    decide_rows_of_wave<EVSRC_SPEED, VEC>(p, tab, nthr, in.W, h0, h1, mask, out, a.n_row);
   } else {
-    decide_rows_of_wave<EVSRC_PLAIN, VEC>(p, tab, nthr, a.W, h0, h1, mask, out, a.n_row);
+    decide_rows_of_wave<EVSRC_PLAIN, VEC>(p, tab, nthr, in.W, h0, h1, mask, out, a.n_row);
   }
 }
 
@@ -369,13 +344,10 @@ extern "C" int paradis_fss_update(const float* fc, int64_t fc_bs, const float* t
                                   const int* clim_index, int K_clim, const int* src_table, const float* thr_table,
                                   const int* half_y, const int* half_x, int64_t* acc_lead, int64_t* n_samples_lead,
                                   void* ws, int B, int C, int S, int H, int W, int K, void* stream) {
-  PD_REQUIRE(B >= 0 && C >= 1 && S >= 1 && S <= FSS_SMAX && H >= 1 && W >= 1,
-             "fss_update: bad shape B=%d C=%d S=%d (at most %d) H=%d W=%d", B, C, S, FSS_SMAX, H, W);
+  int rc = event_shape_check("fss_update", "K_clim", clim, clim_index, K_clim, B, C, S, H, W);
+  if (rc != 0) return rc;
   PD_REQUIRE(W <= FSS_MAX_W, "fss_update: W=%d, at most %d longitudes", W, FSS_MAX_W);
   PD_REQUIRE(K >= 1 && K <= FSS_KMAX, "fss_update: K=%d scales, 1 to %d are allowed", K, FSS_KMAX);
-  PD_REQUIRE((clim != nullptr) == (clim_index != nullptr),
-             "fss_update: clim and clim_index go together (a climatology needs the slot of every sample)");
-  PD_REQUIRE(clim == nullptr || K_clim >= 1, "fss_update: K_clim must be >= 1 with a climatology, got %d", K_clim);
   if (B == 0) return 0;
   PD_REQUIRE(src_table && thr_table && half_y, "fss_update: null table (src_table, thr_table, half_y)");
   WindowArgs wa;
@@ -386,50 +358,29 @@ extern "C" int paradis_fss_update(const float* fc, int64_t fc_bs, const float* t
                FSS_MAX_HY);
     ny_max = std::max(ny_max, wa.hy[k]);
   }
-  DecideArgs a;
-  int nthr_max = 0;
-  for (int s = 0; s < S; ++s) {
-    const int kind = src_table[4 * s], c0 = src_table[4 * s + 1], c1 = src_table[4 * s + 2], nthr = src_table[4 * s + 3];
-    PD_REQUIRE(kind == EVSRC_PLAIN || kind == EVSRC_SPEED || kind == EVSRC_ANOMALY, "fss_update: source %d has kind %d", s,
-               kind);
-    PD_REQUIRE(kind != EVSRC_ANOMALY || clim != nullptr, "fss_update: source %d is an anomaly, but there is no climatology",
-               s);
-    PD_REQUIRE(c0 >= 0 && c0 < C && (kind != EVSRC_SPEED || (c1 >= 0 && c1 < C)),
-               "fss_update: source %d reads channels %d, %d outside [0, %d)", s, c0, c1, C);
-    PD_REQUIRE(nthr >= 1 && nthr <= FSS_TMAX, "fss_update: source %d has %d thresholds, outside [1, %d]", s, nthr, FSS_TMAX);
-    const float sign = thr_table[s * (1 + FSS_TMAX)];
-    PD_REQUIRE(sign == 1.f || sign == -1.f, "fss_update: source %d has sign %g, not +-1", s, (double)sign);
-    a.src[s][0] = kind; a.src[s][1] = c0; a.src[s][2] = kind == EVSRC_SPEED ? c1 : c0; a.src[s][3] = nthr;
-    for (int j = 0; j <= FSS_TMAX; ++j) a.thr[s][j] = thr_table[s * (1 + FSS_TMAX) + j];
-    nthr_max = std::max(nthr_max, nthr);
-  }
-  for (int s = S; s < FSS_SMAX; ++s) {
-    for (int j = 0; j < 4; ++j) a.src[s][j] = 0;
-    for (int j = 0; j <= FSS_TMAX; ++j) a.thr[s][j] = 0.f;
-  }
   PD_REQUIRE(acc_lead != nullptr && n_samples_lead != nullptr, "fss_update: acc_lead / n_samples_lead missing");
   PD_REQUIRE(ws != nullptr && aligned16(ws), "fss_update: ws (workspace) missing or not 16-byte aligned");
   PD_REQUIRE(fc && truth && half_x, "fss_update: null input pointer (fc, truth, half_x)");
-  const int64_t P = (int64_t)H * W;
-  PD_REQUIRE(P < (1ll << 31) - PLANE_PIECE, "fss_update: a plane of %d x %d cells is too large", H, W);
-  PD_REQUIRE(fc_bs >= P * C && truth_bs >= P * C, "fss_update: batch strides shorter than one state");
-  const int rows = decide_rows(W), R = fss_rows();
-  const int64_t pairs = (int64_t)B * S, dgroups = ceil_div64(H, rows), wgroups = ceil_div64(H, R);
+  DecideArgs a;
+  bool vec;
+  rc = event_sources_fill("fss_update", a.in, vec, fc, fc_bs, truth, truth_bs, clim, clim_index, K_clim, src_table,
+                          thr_table, C, S, H, W);
+  if (rc != 0) return rc;
+  int nthr_max = 0;
+  for (int s = 0; s < S; ++s) nthr_max = std::max(nthr_max, a.in.src[s][3]);
+  const int R = fss_rows();
+  const int64_t pairs = (int64_t)B * S, dgroups = a.in.ngroups, wgroups = ceil_div64(H, R);
   PD_REQUIRE(pairs * dgroups < (1ll << 31) && pairs * K * wgroups < (1ll << 31),
              "fss_update: %lld workgroups exceed the grid limit", (long long)std::max(pairs * dgroups, pairs * K * wgroups));
   const int n_row = row_counters(K);
   const int64_t n = (int64_t)S * H * n_row;
   PD_REQUIRE(ceil_div64(n, 256) < (1ll << 31), "fss_update: %lld counters exceed the grid limit", (long long)n);
-  a.fc = fc; a.truth = truth; a.clim = clim; a.clim_index = clim_index;
   a.mask = static_cast<uint16_t*>(ws);
   a.partial = reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + mask_bytes(B, S, H, W));
-  a.fc_bs = fc_bs; a.truth_bs = truth_bs; a.P = P;
-  a.C = C; a.S = S; a.H = H; a.W = W; a.K_clim = K_clim; a.rows = rows; a.ngroups = (int)dgroups; a.n_row = n_row;
+  a.n_row = n_row;
   wa.mask = a.mask; wa.half_x = half_x; wa.partial = a.partial;
   wa.H = H; wa.W = W; wa.K = K; wa.rows = R; wa.ngroups = (int)wgroups; wa.n_row = n_row;
   wa.nx_cap = std::min(FSS_MAX_HX, (W - 1) / 2);
-  const bool vec = (W % 4 == 0) && aligned16(fc) && aligned16(truth) && (fc_bs % 4 == 0) && (truth_bs % 4 == 0) &&
-                   (clim == nullptr || aligned16(clim));
   hipStream_t st = (hipStream_t)stream;
   const dim3 dgrid((unsigned)(pairs * dgroups)), wgrid((unsigned)(pairs * K * wgroups));
   if (vec) hipLaunchKernelGGL(fss_decide_kernel<true>, dgrid, dim3(256), 0, st, a);

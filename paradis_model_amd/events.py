@@ -44,15 +44,15 @@ No CPU fallback: ``update`` needs tensors on the HIP device.  Everything else (a
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import batch_stride, dense_state, sum_over_ranks, workspace
-from .spectrum import band_weights
+from ._leadtable import LeadTable, positive_int, read
+from ._tables import batch_stride, workspace
 
 KINDS = {"plain": 0, "speed": 1, "anomaly": 2}
 BYTES_PER_CELL = {0: 8, 1: 16, 2: 12}          # forecast and truth (and climatology) values of one cell
@@ -163,7 +163,83 @@ def parse_events(who: str, events, names: Sequence[str], with_climatology: bool)
             "_thr": np.ascontiguousarray(thr), "_bytes_per_cell": float(sum(BYTES_PER_CELL[k] for k in kinds))}
 
 
-class EventTable:
+class EventLeadTable(LeadTable):
+    """What ``EventTable`` and ``neighbourhood.FractionsTable`` share: construction up to ``parse_events``, the int64
+    accumulator rows that begin ``{nV, nF[TMAX], nO[TMAX]}`` and ``n_samples``, and the parts of ``counts`` / ``result``
+    that read them.  ``n_lon``: the number of longitudes where the constructor knows it; ``row``: the int64 entries of
+    one accumulator row, given ``tmax``."""
+    IT = "the table"
+    IT_HAS = "the table has"
+
+    def __init__(self, names, lat_deg, n_leads, events, bands, weights, climatology, device, row, n_lon=None):
+        super().__init__(names, n_leads, device)
+        if n_lon is not None:
+            self.W = positive_int(self.who, "n_lon", n_lon)
+        self.lat = self._set_grid(lat_deg, weights, bands)
+        self._set_climatology(climatology)
+        for k, v in parse_events(self.who, events, self.names, self.climatology is not None).items():
+            setattr(self, k, v)
+        with torch.inference_mode(False):
+            self.acc = torch.zeros(self.n_leads, len(self.labels), self.H, row(self.tmax), dtype=torch.int64,
+                                   device=self.device)
+            self.n_samples = torch.zeros(self.n_leads, dtype=torch.int64, device=self.device)
+
+    def reset(self) -> None:
+        self.acc.zero_()
+        self.n_samples.zero_()
+
+    def _counts_head(self, sync_dist: bool):
+        """one device read: ``(a, n_samples, out)`` - the accumulator, the sample counts and ``out`` with ``valid``,
+        ``forecast_yes`` and ``observed_yes``; ``_past`` marks what a subclass adds"""
+        a, n = read(self.acc, self.n_samples, sync_dist)
+        T, TM = self.T, self.tmax
+        out = {"valid": a[..., 0].copy(), "forecast_yes": a[..., 1:1 + T].copy(),
+               "observed_yes": a[..., 1 + TM:1 + TM + T].copy()}
+        return a, n, out
+
+    def _past(self, out: dict, n) -> dict:
+        """-1 past a source's own thresholds (the last axis of every array but ``valid``), then ``n_samples``"""
+        for s, nt in enumerate(self.n_thresholds):
+            for k in out:
+                if k != "valid":
+                    out[k][:, s, ..., nt:] = -1
+        out["n_samples"] = n
+        return out
+
+    def _dead(self, n, shape) -> np.ndarray:
+        """bool ``[n_leads, S, R, T]``: leads never updated, and entries past a source's own thresholds"""
+        dead = np.zeros(shape, bool)
+        dead[n == 0] = True
+        for s, nt in enumerate(self.n_thresholds):
+            dead[:, s, :, nt:] = True
+        return dead
+
+    def _finish(self, res: dict, n, sV) -> dict:
+        """``valid_fraction`` from ``sV = sum_h wb nV`` ``[n_leads, S, R]``, and what every result ends with"""
+        seen = n.astype(np.float64)[:, None, None] * float(self.W or 0) * self.band_w.sum(axis=1)[None, None, :]
+        with np.errstate(all="ignore"):
+            res["valid_fraction"] = sV / np.where(seen > 0, seen, np.nan)
+        res["count"] = n.copy()
+        res["labels"] = list(self.labels)
+        res["thresholds"] = [list(t) for t in self.thresholds]
+        res["directions"] = list(self.directions)
+        res["bands"] = list(self.bands)
+        return res
+
+
+def lookup(who: str, result: dict, label: str, band: Optional[str]):
+    """``(s, r, band)``: where ``label`` and ``band`` (default the first) are in a result, for ``table``"""
+    labels: List[str] = list(result["labels"])
+    bands: List[str] = list(result["bands"])
+    if str(label) not in labels:
+        raise ValueError(f"{who}.table: event '{label}' is not among the table's labels")
+    band = bands[0] if band is None else str(band)
+    if band not in bands:
+        raise ValueError(f"{who}.table: band '{band}' is not among the table's bands")
+    return labels.index(str(label)), bands.index(band), band
+
+
+class EventTable(EventLeadTable):
     """Per-lead contingency tables of threshold events, accumulated on the device (module docstring for the definitions;
     invalid - non-finite - cells are counted in no class, unlike ``Scorecard``, where NaN propagates).
 
@@ -192,62 +268,14 @@ class EventTable:
     ``scores(a, b, c, d)``: host only, tables -> the nine scores.  ``table(result, label, ...)``: plain text for logs.
     ``reset()`` clears the accumulators."""
 
+    NOUN = "the event table"
+    HAS = "the event table has"
+    NEEDS = "an event table needs"
+
     def __init__(self, names: Sequence[str], lat_deg, n_leads: int, events: dict, *, bands: Optional[dict] = None,
                  weights=None, climatology: Optional[torch.Tensor] = None, device="cuda"):
-        self.names = [str(n) for n in names]
-        C = len(self.names)
-        if C < 1:
-            raise ValueError("EventTable: names must list at least one channel")
-        if isinstance(n_leads, bool) or int(n_leads) != n_leads or int(n_leads) < 1:
-            raise ValueError(f"EventTable: n_leads must be an integer >= 1, got {n_leads!r}")
-        self.n_leads = int(n_leads)
-        self.device = torch.device(device)
-        lat = torch.as_tensor(lat_deg).detach().reshape(-1).double().cpu().numpy()
-        H = lat.size
-        if H < 1 or not np.isfinite(lat).all() or np.abs(lat).max() > 90.0:
-            raise ValueError("EventTable: lat_deg must be a vector [H] of finite latitudes in [-90, 90] degrees")
-        if weights is None:
-            w64 = np.clip(np.cos(np.deg2rad(lat)), 0.0, None)           # (cos(+-90 deg) in double is 6e-17, not 0)
-            w64[np.abs(lat) == 90.0] = 0.0
-        else:
-            w = torch.as_tensor(weights).detach().reshape(-1)
-            if w.numel() != H or not w.is_floating_point():
-                raise ValueError(f"EventTable: weights must be a floating-point vector [{H}]")
-            w64 = w.double().cpu().numpy()
-            if not np.isfinite(w64).all() or (w64 < 0).any() or not w64.sum() > 0.0:
-                raise ValueError("EventTable: weights must be finite, >= 0 and not all zero")
-        if bands is None:
-            bands = {"global": (-90.0, 90.0)}
-        if not isinstance(bands, dict) or len(bands) < 1:
-            raise ValueError("EventTable: bands must be a non-empty dict name -> (lat_lo, lat_hi)")
-        self.bands = [str(b) for b in bands]
-        try:
-            self.band_w = band_weights(lat, w64, bands)                  # double [R, H], on the host
-        except ValueError as e:
-            raise ValueError(str(e).replace("Spectra:", "EventTable:")) from None
-        self.H = H
-        self.W: Optional[int] = None
-        self.climatology = None
-        if climatology is not None:
-            cl = climatology
-            if not isinstance(cl, torch.Tensor) or cl.dim() != 4 or cl.dtype != torch.float32 or \
-                    cl.shape[0] < 1 or cl.shape[1] != C or cl.shape[2] != H or not cl.is_contiguous():
-                raise ValueError(f"EventTable: climatology must be a contiguous float32 [K, {C}, {H}, W] tensor")
-            if cl.device.type != self.device.type:
-                raise ValueError(f"EventTable: climatology lives on {cl.device}, the table on {self.device}")
-            self.climatology = cl
-        self._parse(events)
-        S = len(self.labels)
-        with torch.inference_mode(False):
-            self.acc = torch.zeros(self.n_leads, S, H, 1 + 3 * self.tmax, dtype=torch.int64, device=self.device)
-            self.n_samples = torch.zeros(self.n_leads, dtype=torch.int64, device=self.device)
-        self._ws: Dict[tuple, torch.Tensor] = {}      # (device, stream) -> workspace
-        self._slot0: Dict[int, torch.Tensor] = {}     # B -> zeros [B] int32: the index of a one-slot climatology
-
-    def _parse(self, events) -> None:
-        """labels, kinds, thresholds, directions and the two host tables of the entry point"""
-        for k, v in parse_events("EventTable", events, self.names, self.climatology is not None).items():
-            setattr(self, k, v)
+        super().__init__(names, lat_deg, n_leads, events, bands, weights, climatology, device,
+                         row=lambda tmax: 1 + 3 * tmax)
 
     def bind(self, W: int) -> None:
         """states the number of longitudes ahead of the first ``update`` (which otherwise does it); ``valid_fraction``
@@ -258,41 +286,9 @@ class EventTable:
             raise ValueError(f"EventTable.bind: the table is bound to {self.W} longitudes already")
         self.W = int(W)
 
-    def _check(self, lead, forecast, truth, clim_index):
-        """argument checks of ``update``; returns (B, C, H, W)"""
-        if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < self.n_leads:
-            raise ValueError(f"EventTable.update: lead must be an integer in [0, {self.n_leads}), got {lead!r}")
-        C, H = len(self.names), self.H
-        for what, t in (("forecast", forecast), ("truth", truth)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 4:
-                raise ValueError(f"EventTable.update: {what} must be a [B, C, H, W] tensor")
-            if t.dtype != torch.float32:
-                raise ValueError(f"EventTable.update: {what} must be float32, got {t.dtype}")
-        B, Cf, Hf, W = forecast.shape
-        if (Cf, Hf) != (C, H) or W < 1:
-            raise ValueError(f"EventTable.update: forecast is {tuple(forecast.shape)}; the table has {C} channels "
-                             f"and {H} latitudes")
-        if truth.shape != forecast.shape:
-            raise ValueError(f"EventTable.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
+    def _check_longitudes(self, W: int) -> None:
         if self.W is not None and W != self.W:
             raise ValueError(f"EventTable.update: forecast has {W} longitudes, the table is bound to {self.W}")
-        dense_state(forecast, "forecast", "EventTable.update")
-        dense_state(truth, "truth", "EventTable.update")
-        if self.climatology is None:
-            if clim_index is not None:
-                raise ValueError("EventTable.update: clim_index given, but the table has no climatology")
-        else:
-            if self.climatology.shape[3] != W:
-                raise ValueError(f"EventTable.update: forecast has {W} longitudes, the climatology "
-                                 f"{self.climatology.shape[3]}")
-            if clim_index is None:
-                if self.climatology.shape[0] != 1:
-                    raise ValueError(f"EventTable.update: clim_index is needed to choose among the "
-                                     f"{self.climatology.shape[0]} climatology slots")
-            elif not isinstance(clim_index, torch.Tensor) or clim_index.dtype != torch.int32 or \
-                    tuple(clim_index.shape) != (B,):
-                raise ValueError(f"EventTable.update: clim_index must be an int32 tensor [{B}]")
-        return B, C, H, W
 
     def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
                clim_index: Optional[torch.Tensor] = None) -> None:
@@ -305,38 +301,18 @@ class EventTable:
         if self.W is None:
             self.bind(W)
         clim = self.climatology
-        if clim is not None:
-            if clim_index is None:
-                if B not in self._slot0:
-                    with torch.inference_mode(False):
-                        self._slot0[B] = torch.zeros(B, dtype=torch.int32, device=forecast.device)
-                clim_index = self._slot0[B]
-            if not clim_index.is_cuda:
-                raise ValueError("EventTable.update: clim_index must live on the device")
-            clim_index = clim_index.contiguous()         # a column of [B, n_stored] becomes dense; no host wait
+        clim_index, K = self._clim_args(clim_index, forecast)
         P, S = H * W, len(self.labels)
         ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_events_ws_bytes(B, S, H, W)))
         _lib.call("events_update", self._bytes_per_cell * B * P, dptr(forecast), batch_stride(forecast, C * P),
-                  dptr(truth), batch_stride(truth, C * P), dptr(clim), dptr(clim_index) if clim is not None else None,
-                  clim.shape[0] if clim is not None else 0, self._src.ctypes.data, self._thr.ctypes.data,
-                  dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]), dptr(ws), B, C, S, H, W, stream_ptr())
-
-    def reset(self) -> None:
-        self.acc.zero_()
-        self.n_samples.zero_()
+                  dptr(truth), batch_stride(truth, C * P), dptr(clim), dptr(clim_index), K, self._src.ctypes.data,
+                  self._thr.ctypes.data, dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]), dptr(ws), B, C, S,
+                  H, W, stream_ptr())
 
     def counts(self, sync_dist: bool = False) -> dict:
-        # (one tensor: the accumulators and, behind them, the sample counts - one all-reduce, one device read)
-        flat = sum_over_ranks(torch.cat([self.acc.reshape(-1), self.n_samples]), sync_dist).numpy()
-        a = flat[:self.acc.numel()].reshape(tuple(self.acc.shape))
-        T, TM = self.T, self.tmax
-        out = {"valid": a[..., 0].copy(), "forecast_yes": a[..., 1:1 + T].copy(),
-               "observed_yes": a[..., 1 + TM:1 + TM + T].copy(), "both": a[..., 1 + 2 * TM:1 + 2 * TM + T].copy(),
-               "n_samples": flat[self.acc.numel():].copy()}
-        for s, n in enumerate(self.n_thresholds):
-            for k in ("forecast_yes", "observed_yes", "both"):
-                out[k][:, s, :, n:] = -1
-        return out
+        a, n, out = self._counts_head(sync_dist)
+        out["both"] = a[..., 1 + 2 * self.tmax:1 + 2 * self.tmax + self.T].copy()
+        return self._past(out, n)
 
     def result(self, sync_dist: bool = False) -> dict:
         cnt = self.counts(sync_dist)
@@ -349,22 +325,10 @@ class EventTable:
         res = dict(zip(TABLES, (a, b, c, d)))
         res.update(scores(a, b, c, d))
         n = cnt["n_samples"]
-        dead = np.zeros(a.shape, bool)
-        dead[n == 0] = True                                               # leads never updated
-        for s, nt in enumerate(self.n_thresholds):
-            dead[:, s, :, nt:] = True                                     # past a source's own thresholds
+        dead = self._dead(n, a.shape)
         for k in TABLES + SCORES:
             res[k] = np.where(dead, np.nan, res[k])
-        seen = n.astype(np.float64)[:, None, None] * float(self.W or 0) * wb.sum(axis=1)[None, None, :]
-        with np.errstate(all="ignore"):
-            vf = np.einsum("rh,lsh->lsr", wb, nV) / np.where(seen > 0, seen, np.nan)
-        res["valid_fraction"] = vf
-        res["count"] = n.copy()
-        res["labels"] = list(self.labels)
-        res["thresholds"] = [list(t) for t in self.thresholds]
-        res["directions"] = list(self.directions)
-        res["bands"] = list(self.bands)
-        return res
+        return self._finish(res, n, np.einsum("rh,lsh->lsr", wb, nV))
 
     scores = staticmethod(scores)
 
@@ -372,17 +336,10 @@ class EventTable:
     def table(result: dict, label: str, band: Optional[str] = None,
               metrics: Sequence[str] = ("frequency_bias", "csi", "ets", "sedi")) -> str:
         """plain text, one block per metric: a row per lead, a column per threshold of ``label``"""
-        labels: List[str] = list(result["labels"])
-        bands: List[str] = list(result["bands"])
-        if str(label) not in labels:
-            raise ValueError(f"EventTable.table: event '{label}' is not among the table's labels")
-        band = bands[0] if band is None else str(band)
-        if band not in bands:
-            raise ValueError(f"EventTable.table: band '{band}' is not among the table's bands")
+        s, r, band = lookup("EventTable", result, label, band)
         for m in metrics:
             if m not in TABLES + SCORES:
                 raise ValueError(f"EventTable.table: '{m}' is not among {TABLES + SCORES}")
-        s, r = labels.index(str(label)), bands.index(band)
         thr = result["thresholds"][s]
         op = ">=" if result["directions"][s] == "ge" else "<="
         lines = [f"{label} / {band}"]

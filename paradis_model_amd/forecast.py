@@ -208,6 +208,12 @@ def chunk_plan(forecast_steps: int, output_frequency: int, write_every_n: Option
 
 
 # ---------------------------------------------------------------------------------- the predict loop
+def _passed(scorecard, spectra, events, fractions) -> list:
+    """the verification tables given to ``run`` (``_leadtable.LeadTable``: each brings its phrases and whether its
+    ``update`` takes ``clim_index``), in the order of their refusals and of their launches"""
+    return [t for t in (scorecard, spectra, events, fractions) if t is not None]
+
+
 class Forecaster:
     """``LitParadis.predict_step`` (reference trainer.py:731-815) on the device.
 
@@ -281,33 +287,21 @@ class Forecaster:
         """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=...)``, before the rollout starts;
         returns the forecaster's ``[B, 1, C, H, W]`` scratch tensor for a model-space truth (``truth_normalized=True``),
         else None"""
-        if scorecard is None and spectra is None and events is None and fractions is None:
+        tables = _passed(scorecard, spectra, events, fractions)
+        if not tables:
             if truth is not None or clim_index is not None or truth_normalized:
                 raise ValueError("Forecaster.run: truth, truth_normalized and clim_index go with a scorecard")
             return None
-        if scorecard is None and events is None and fractions is None and clim_index is not None:
+        if clim_index is not None and not any(t.TAKES_CLIM_INDEX for t in tables):
             raise ValueError("Forecaster.run: clim_index goes with a scorecard")
         if truth.dim() != 5 or tuple(truth.shape) != (B, n_stored, C, H, W) or truth.dtype != torch.float32:
             raise ValueError(f"Forecaster.run: truth must be float32 {(B, n_stored, C, H, W)} (n_stored = {n_stored} "
                              f"stored states), got {truth.dtype} {tuple(truth.shape)}")
-        if scorecard is not None and scorecard.n_leads < n_stored:
-            raise ValueError(f"Forecaster.run: the scorecard has {scorecard.n_leads} leads, the rollout stores {n_stored}")
-        if scorecard is not None and list(scorecard.names) != list(self.spec.names):
-            raise ValueError("Forecaster.run: the scorecard's names are not the chunk's channel names (PostSpec.names)")
-        if spectra is not None and spectra.n_leads < n_stored:
-            raise ValueError(f"Forecaster.run: the spectra have {spectra.n_leads} leads, the rollout stores {n_stored}")
-        if spectra is not None and list(spectra.all_names) != list(self.spec.names):
-            raise ValueError("Forecaster.run: the spectra's names are not the chunk's channel names (PostSpec.names)")
-        if events is not None and events.n_leads < n_stored:
-            raise ValueError(f"Forecaster.run: the event table has {events.n_leads} leads, the rollout stores {n_stored}")
-        if events is not None and list(events.names) != list(self.spec.names):
-            raise ValueError("Forecaster.run: the event table's names are not the chunk's channel names (PostSpec.names)")
-        if fractions is not None and fractions.n_leads < n_stored:
-            raise ValueError(f"Forecaster.run: the fractions table has {fractions.n_leads} leads, the rollout stores "
-                             f"{n_stored}")
-        if fractions is not None and list(fractions.names) != list(self.spec.names):
-            raise ValueError("Forecaster.run: the fractions table's names are not the chunk's channel names "
-                             "(PostSpec.names)")
+        for t in tables:
+            if t.n_leads < n_stored:
+                raise ValueError(f"Forecaster.run: {t.HAS} {t.n_leads} leads, the rollout stores {n_stored}")
+            if list(t.all_names) != list(self.spec.names):
+                raise ValueError(f"Forecaster.run: {t.NOUN}'s names are not the chunk's channel names (PostSpec.names)")
         if clim_index is not None and (clim_index.dtype != torch.int32 or tuple(clim_index.shape) != (B, n_stored)):
             raise ValueError(f"Forecaster.run: clim_index must be int32 {(B, n_stored)}, got {clim_index.dtype} "
                              f"{tuple(clim_index.shape)}")
@@ -349,14 +343,10 @@ class Forecaster:
             forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
             truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None, encoder=None, init=None,
             spectra=None, events=None, fractions=None):
-        if scorecard is not None and truth is None:          # (a host-side refusal, in front of the device checks)
-            raise ValueError("Forecaster.run: a scorecard needs truth [B, n_stored, C, H, W] on the device")
-        if spectra is not None and truth is None:
-            raise ValueError("Forecaster.run: spectra need truth [B, n_stored, C, H, W] on the device")
-        if events is not None and truth is None:
-            raise ValueError("Forecaster.run: an event table needs truth [B, n_stored, C, H, W] on the device")
-        if fractions is not None and truth is None:
-            raise ValueError("Forecaster.run: a fractions table needs truth [B, n_stored, C, H, W] on the device")
+        tables = _passed(scorecard, spectra, events, fractions)
+        for t in tables:                                     # (host-side refusals, in front of the device checks)
+            if truth is None:
+                raise ValueError(f"Forecaster.run: {t.NEEDS} truth [B, n_stored, C, H, W] on the device")
         require_hip(input_data, forcings, constants)
         S = int(forcings.shape[1] if forecast_steps is None else forecast_steps)
         if forcings.shape[1] < S:
@@ -395,22 +385,14 @@ class Forecaster:
                     views = chunks.open(next(sizes))
                     d, dd = views["state"], views.get("dew")
                 postprocess(out, self.spec, self.lat_deg, self.lon_deg, d, p.slot, dd)
-                if scorecard is not None or spectra is not None or events is not None or fractions is not None:
+                if tables:
                     t = truth[:, i_stored]
                     if truth_phys is not None:             # a model-space truth: to physical units first
                         postprocess(t, self.spec, self.lat_deg, self.lon_deg, truth_phys, 0)
                         t = truth_phys[:, 0]
-                    if scorecard is not None:
-                        scorecard.update(i_stored, d[:, p.slot], t,
-                                         None if clim_index is None else clim_index[:, i_stored])
-                    if spectra is not None:
-                        spectra.update(i_stored, d[:, p.slot], t)
-                    if events is not None:
-                        events.update(i_stored, d[:, p.slot], t,
-                                      None if clim_index is None else clim_index[:, i_stored])
-                    if fractions is not None:
-                        fractions.update(i_stored, d[:, p.slot], t,
-                                         None if clim_index is None else clim_index[:, i_stored])
+                    k = None if clim_index is None else clim_index[:, i_stored]
+                    for table in tables:                   # (scorecard, spectra, events, fractions: the launch order)
+                        table.update(i_stored, d[:, p.slot], t, *((k,) if table.TAKES_CLIM_INDEX else ()))
                 i_stored += 1
             if p.flush is not None:
                 start, n = p.flush

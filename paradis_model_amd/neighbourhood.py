@@ -46,16 +46,15 @@ No CPU fallback: ``update`` needs tensors on the HIP device.  Everything else wo
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import batch_stride, dense_state, sum_over_ranks, workspace
-from .events import _ratio, parse_events
-from .spectrum import band_weights
+from ._tables import batch_stride, workspace
+from .events import EventLeadTable, _ratio, lookup, parse_events          # noqa: F401  (parse_events: importable from here)
 
 WHO = "FractionsTable"
 
@@ -111,7 +110,7 @@ def skilful_scale(result: dict) -> np.ndarray:
     return np.where(ok.any(axis=3), first, -1).astype(np.int64)
 
 
-class FractionsTable:
+class FractionsTable(EventLeadTable):
     """Per-lead fractions skill scores over several window sizes, their integer sums accumulated on the device (module
     docstring for the definitions; an invalid - non-finite - cell is a non-event in both fields).
 
@@ -136,57 +135,18 @@ class FractionsTable:
     ``bands``, ``scales`` and ``window_cells [K, H]``.  ``skilful_scale(result)``; ``table(result, label, band=None)``:
     plain text.  ``reset()`` clears the accumulators."""
 
+    NOUN = "the fractions table"
+    HAS = "the fractions table has"
+    NEEDS = "a fractions table needs"
+
     def __init__(self, names: Sequence[str], lat_deg, n_lon: int, n_leads: int, events: dict, scales: Sequence[int],
                  lon_scaling: str = "cells", half_x=None, bands: Optional[dict] = None, weights=None,
                  climatology: Optional[torch.Tensor] = None, device="cuda"):
-        self.names = [str(n) for n in names]
-        C = len(self.names)
-        if C < 1:
-            raise ValueError(f"{WHO}: names must list at least one channel")
-        if isinstance(n_leads, bool) or int(n_leads) != n_leads or int(n_leads) < 1:
-            raise ValueError(f"{WHO}: n_leads must be an integer >= 1, got {n_leads!r}")
-        if isinstance(n_lon, bool) or int(n_lon) != n_lon or int(n_lon) < 1:
-            raise ValueError(f"{WHO}: n_lon must be an integer >= 1, got {n_lon!r}")
-        self.n_leads, self.W = int(n_leads), int(n_lon)
-        self.device = torch.device(device)
-        lat = torch.as_tensor(lat_deg).detach().reshape(-1).double().cpu().numpy()
-        H = lat.size
-        if H < 1 or not np.isfinite(lat).all() or np.abs(lat).max() > 90.0:
-            raise ValueError(f"{WHO}: lat_deg must be a vector [H] of finite latitudes in [-90, 90] degrees")
-        if weights is None:
-            w64 = np.clip(np.cos(np.deg2rad(lat)), 0.0, None)           # (cos(+-90 deg) in double is 6e-17, not 0)
-            w64[np.abs(lat) == 90.0] = 0.0
-        else:
-            w = torch.as_tensor(weights).detach().reshape(-1)
-            if w.numel() != H or not w.is_floating_point():
-                raise ValueError(f"{WHO}: weights must be a floating-point vector [{H}]")
-            w64 = w.double().cpu().numpy()
-            if not np.isfinite(w64).all() or (w64 < 0).any() or not w64.sum() > 0.0:
-                raise ValueError(f"{WHO}: weights must be finite, >= 0 and not all zero")
-        if bands is None:
-            bands = {"global": (-90.0, 90.0)}
-        if not isinstance(bands, dict) or len(bands) < 1:
-            raise ValueError(f"{WHO}: bands must be a non-empty dict name -> (lat_lo, lat_hi)")
-        self.bands = [str(b) for b in bands]
-        try:
-            self.band_w = band_weights(lat, w64, bands)                  # double [R, H], on the host
-        except ValueError as e:
-            raise ValueError(str(e).replace("Spectra:", f"{WHO}:")) from None
-        self.H = H
-        self.climatology = None
-        if climatology is not None:
-            cl = climatology
-            if not isinstance(cl, torch.Tensor) or cl.dim() != 4 or cl.dtype != torch.float32 or \
-                    cl.shape[0] < 1 or cl.shape[1] != C or cl.shape[2] != H or cl.shape[3] != self.W or \
-                    not cl.is_contiguous():
-                raise ValueError(f"{WHO}: climatology must be a contiguous float32 [K, {C}, {H}, {self.W}] tensor")
-            if cl.device.type != self.device.type:
-                raise ValueError(f"{WHO}: climatology lives on {cl.device}, the table on {self.device}")
-            self.climatology = cl
-        for k, v in parse_events(WHO, events, self.names, self.climatology is not None).items():
-            setattr(self, k, v)
         lim = limits()
         self.kmax = lim["max_scales"]
+        super().__init__(names, lat_deg, n_leads, events, bands, weights, climatology, device,
+                         row=lambda tmax: 1 + 2 * tmax + 3 * self.kmax * tmax, n_lon=n_lon)
+        H, lat = self.H, self.lat
         try:
             sc = [s for s in scales]
         except TypeError:
@@ -210,45 +170,11 @@ class FractionsTable:
             self.half_x = np.ascontiguousarray(hx.astype(np.int32))
         self._half_y = np.ascontiguousarray(np.asarray(self.scales, np.int32))
         self.window_cells = window_cells(self.scales, self.half_x, H)
-        S = len(self.labels)
         self.head = 1 + 2 * self.tmax
-        with torch.inference_mode(False):
-            self.acc = torch.zeros(self.n_leads, S, H, self.head + 3 * self.kmax * self.tmax, dtype=torch.int64,
-                                   device=self.device)
-            self.n_samples = torch.zeros(self.n_leads, dtype=torch.int64, device=self.device)
-        self._ws: Dict[tuple, torch.Tensor] = {}      # (device, stream) -> workspace
-        self._slot0: Dict[int, torch.Tensor] = {}     # B -> zeros [B] int32: the index of a one-slot climatology
         self._half_x_dev: Dict[str, torch.Tensor] = {}     # device -> half_x there
 
     def _check(self, lead, forecast, truth, clim_index):
-        """argument checks of ``update``; returns (B, C, H, W)"""
-        if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < self.n_leads:
-            raise ValueError(f"{WHO}.update: lead must be an integer in [0, {self.n_leads}), got {lead!r}")
-        C, H = len(self.names), self.H
-        for what, t in (("forecast", forecast), ("truth", truth)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 4:
-                raise ValueError(f"{WHO}.update: {what} must be a [B, C, H, W] tensor")
-            if t.dtype != torch.float32:
-                raise ValueError(f"{WHO}.update: {what} must be float32, got {t.dtype}")
-        B, Cf, Hf, W = forecast.shape
-        if (Cf, Hf, W) != (C, H, self.W):
-            raise ValueError(f"{WHO}.update: forecast is {tuple(forecast.shape)}; the table has {C} channels, "
-                             f"{H} latitudes and {self.W} longitudes")
-        if truth.shape != forecast.shape:
-            raise ValueError(f"{WHO}.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
-        dense_state(forecast, "forecast", f"{WHO}.update")
-        dense_state(truth, "truth", f"{WHO}.update")
-        if self.climatology is None:
-            if clim_index is not None:
-                raise ValueError(f"{WHO}.update: clim_index given, but the table has no climatology")
-        elif clim_index is None:
-            if self.climatology.shape[0] != 1:
-                raise ValueError(f"{WHO}.update: clim_index is needed to choose among the "
-                                 f"{self.climatology.shape[0]} climatology slots")
-        elif not isinstance(clim_index, torch.Tensor) or clim_index.dtype != torch.int32 or \
-                tuple(clim_index.shape) != (B,):
-            raise ValueError(f"{WHO}.update: clim_index must be an int32 tensor [{B}]")
-        return B, C, H, W
+        return super()._check(lead, forecast, truth, clim_index, n_lon=self.W)
 
     def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
                clim_index: Optional[torch.Tensor] = None) -> None:
@@ -259,15 +185,7 @@ class FractionsTable:
         if B == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
             return
         clim = self.climatology
-        if clim is not None:
-            if clim_index is None:
-                if B not in self._slot0:
-                    with torch.inference_mode(False):
-                        self._slot0[B] = torch.zeros(B, dtype=torch.int32, device=forecast.device)
-                clim_index = self._slot0[B]
-            if not clim_index.is_cuda:
-                raise ValueError(f"{WHO}.update: clim_index must live on the device")
-            clim_index = clim_index.contiguous()         # a column of [B, n_stored] becomes dense; no host wait
+        clim_index, K_clim = self._clim_args(clim_index, forecast)
         dev = str(forecast.device)
         if dev not in self._half_x_dev:
             with torch.inference_mode(False):
@@ -276,8 +194,7 @@ class FractionsTable:
         ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_fss_ws_bytes(B, S, H, W, K)))
         try:
             _lib.call("fss_update", self._bytes_per_cell * B * P, dptr(forecast), batch_stride(forecast, C * P),
-                      dptr(truth), batch_stride(truth, C * P), dptr(clim),
-                      dptr(clim_index) if clim is not None else None, clim.shape[0] if clim is not None else 0,
+                      dptr(truth), batch_stride(truth, C * P), dptr(clim), dptr(clim_index), K_clim,
                       self._src.ctypes.data, self._thr.ctypes.data, self._half_y.ctypes.data,
                       dptr(self._half_x_dev[dev]), dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]),
                       dptr(ws), B, C, S, H, W, K, stream_ptr())
@@ -286,25 +203,12 @@ class FractionsTable:
                 raise ValueError(f"{WHO}.update: {_lib.last_error()}") from None
             raise
 
-    def reset(self) -> None:
-        self.acc.zero_()
-        self.n_samples.zero_()
-
     def counts(self, sync_dist: bool = False) -> dict:
-        # (one tensor: the accumulators and, behind them, the sample counts - one all-reduce, one device read)
-        flat = sum_over_ranks(torch.cat([self.acc.reshape(-1), self.n_samples]), sync_dist).numpy()
-        a = flat[:self.acc.numel()].reshape(tuple(self.acc.shape))
+        a, n, out = self._counts_head(sync_dist)
         T, TM, K = self.T, self.tmax, len(self.scales)
         win = a[..., self.head:self.head + 3 * K * TM].reshape(a.shape[:3] + (K, TM, 3))[..., :T, :]
-        out = {"valid": a[..., 0].copy(), "forecast_yes": a[..., 1:1 + T].copy(),
-               "observed_yes": a[..., 1 + TM:1 + TM + T].copy(), "ff": win[..., 0].copy(), "oo": win[..., 1].copy(),
-               "fo": win[..., 2].copy(), "n_samples": flat[self.acc.numel():].copy()}
-        for s, n in enumerate(self.n_thresholds):
-            for k in ("forecast_yes", "observed_yes"):
-                out[k][:, s, :, n:] = -1
-            for k in ("ff", "oo", "fo"):
-                out[k][:, s, :, :, n:] = -1
-        return out
+        out.update(ff=win[..., 0].copy(), oo=win[..., 1].copy(), fo=win[..., 2].copy())
+        return self._past(out, n)
 
     def result(self, sync_dist: bool = False) -> dict:
         cnt = self.counts(sync_dist)
@@ -321,22 +225,12 @@ class FractionsTable:
         res = {"fss": 1.0 - _ratio(fbs, ref), "fbs": fbs, "fbs_ref": ref, "base_rate": base,
                "frequency_bias": _ratio(sF, sO), "fss_uniform": 0.5 + base / 2.0}
         n = cnt["n_samples"]
-        dead = np.zeros(sF.shape, bool)
-        dead[n == 0] = True                                               # leads never updated
-        for s, nt in enumerate(self.n_thresholds):
-            dead[:, s, :, nt:] = True                                     # past a source's own thresholds
+        dead = self._dead(n, sF.shape)
         for k in ("base_rate", "frequency_bias", "fss_uniform"):
             res[k] = np.where(dead, np.nan, res[k])
         for k in ("fss", "fbs", "fbs_ref"):
             res[k] = np.where(dead[:, :, :, None, :], np.nan, res[k])
-        seen = n.astype(np.float64)[:, None, None] * float(self.W) * wb.sum(axis=1)[None, None, :]
-        with np.errstate(all="ignore"):
-            res["valid_fraction"] = sV / np.where(seen > 0, seen, np.nan)
-        res["count"] = n.copy()
-        res["labels"] = list(self.labels)
-        res["thresholds"] = [list(t) for t in self.thresholds]
-        res["directions"] = list(self.directions)
-        res["bands"] = list(self.bands)
+        self._finish(res, n, sV)
         res["scales"] = list(self.scales)
         res["window_cells"] = self.window_cells.copy()
         return res
@@ -347,14 +241,7 @@ class FractionsTable:
     def table(result: dict, label: str, band: Optional[str] = None) -> str:
         """plain text, one block per threshold of ``label``: a row per lead, a column per scale (its latitude half-width
         in rows), then ``fss_uniform`` and the index of the skilful scale"""
-        labels: List[str] = list(result["labels"])
-        bands: List[str] = list(result["bands"])
-        if str(label) not in labels:
-            raise ValueError(f"{WHO}.table: event '{label}' is not among the table's labels")
-        band = bands[0] if band is None else str(band)
-        if band not in bands:
-            raise ValueError(f"{WHO}.table: band '{band}' is not among the table's bands")
-        s, r = labels.index(str(label)), bands.index(band)
+        s, r, band = lookup(WHO, result, label, band)
         op = ">=" if result["directions"][s] == "ge" else "<="
         first = skilful_scale(result)
         lines = [f"{label} / {band}"]

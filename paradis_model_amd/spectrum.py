@@ -35,14 +35,15 @@ No CPU fallback: ``update`` needs tensors on the HIP device.  The host side (arg
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import batch_stride, dense_state, sum_over_ranks, workspace
+from ._leadtable import LeadTable, band_weights, read          # noqa: F401  (band_weights: importable from here)
+from ._tables import batch_stride, workspace
 
 ACC_FIELDS = 3          # {sum S_ff, sum S_tt, sum S_ft}
 QUANTITIES = ("power_forecast", "power_truth", "cospectrum", "ratio", "coherence", "error_power")
@@ -65,26 +66,7 @@ def twiddle_table(W: int) -> np.ndarray:
     return np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)
 
 
-def band_weights(lat_deg, weights, bands) -> np.ndarray:
-    """double ``[R, H]``: ``weights[h]`` where ``lat_lo <= lat_deg[h] <= lat_hi`` (inclusive), 0 elsewhere"""
-    lat = np.asarray(lat_deg, np.float64).reshape(-1)
-    w = np.asarray(weights, np.float64).reshape(-1)
-    rows = []
-    for name, edges in bands.items():
-        try:
-            lo, hi = (float(v) for v in edges)
-        except (TypeError, ValueError):
-            raise ValueError(f"Spectra: band '{name}' must be (lat_lo, lat_hi) in degrees, got {edges!r}") from None
-        if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
-            raise ValueError(f"Spectra: band '{name}' must have finite lat_lo <= lat_hi, got {edges!r}")
-        row = np.where((lat >= lo) & (lat <= hi), w, 0.0)
-        if not row.sum() > 0.0:
-            raise ValueError(f"Spectra: band '{name}' {edges!r} holds no row of non-zero weight")
-        rows.append(row)
-    return np.ascontiguousarray(np.stack(rows))
-
-
-class Spectra:
+class Spectra(LeadTable):
     """Per-lead zonal power spectra of a rollout and its truth, accumulated on the device (module docstring for the
     formulas; the project's own definition, not pinned against WeatherBench-2).
 
@@ -108,36 +90,15 @@ class Spectra:
     it: the number of longitudes is not a constructor argument).  ``effective_resolution(result, threshold=0.5)`` and
     ``table(result, channel, band=...)`` are host-only."""
 
+    IT = NOUN = "the spectra"
+    IT_HAS = HAS = "the spectra have"
+    NEEDS = "spectra need"
+    TAKES_CLIM_INDEX = False
+
     def __init__(self, names: Sequence[str], lat_deg, n_leads: int, *, bands: Optional[dict] = None, weights=None,
                  channels: Optional[Sequence[str]] = None, device="cuda"):
-        self.all_names = [str(n) for n in names]
-        C = len(self.all_names)
-        if C < 1:
-            raise ValueError("Spectra: names must list at least one channel")
-        if isinstance(n_leads, bool) or int(n_leads) != n_leads or int(n_leads) < 1:
-            raise ValueError(f"Spectra: n_leads must be an integer >= 1, got {n_leads!r}")
-        self.n_leads = int(n_leads)
-        self.device = torch.device(device)
-        lat = torch.as_tensor(lat_deg).detach().reshape(-1).double().cpu().numpy()
-        H = lat.size
-        if H < 1 or not np.isfinite(lat).all() or np.abs(lat).max() > 90.0:
-            raise ValueError("Spectra: lat_deg must be a vector [H] of finite latitudes in [-90, 90] degrees")
-        if weights is None:
-            w64 = np.clip(np.cos(np.deg2rad(lat)), 0.0, None)           # (cos(+-90 deg) in double is 6e-17, not 0)
-            w64[np.abs(lat) == 90.0] = 0.0
-        else:
-            w = torch.as_tensor(weights).detach().reshape(-1)
-            if w.numel() != H or not w.is_floating_point():
-                raise ValueError(f"Spectra: weights must be a floating-point vector [{H}]")
-            w64 = w.double().cpu().numpy()
-            if not np.isfinite(w64).all() or (w64 < 0).any() or not w64.sum() > 0.0:
-                raise ValueError("Spectra: weights must be finite, >= 0 and not all zero")
-        if bands is None:
-            bands = {"global": (-90.0, 90.0)}
-        if not isinstance(bands, dict) or len(bands) < 1:
-            raise ValueError("Spectra: bands must be a non-empty dict name -> (lat_lo, lat_hi)")
-        self.bands = [str(b) for b in bands]
-        self.band_w = band_weights(lat, w64, bands)                      # double [R, H], on the host
+        super().__init__(names, n_leads, device)
+        self._set_grid(lat_deg, weights, bands)
         chosen = self.all_names if channels is None else [str(c) for c in channels]
         if len(chosen) < 1:
             raise ValueError("Spectra: channels must name at least one channel")
@@ -148,15 +109,12 @@ class Spectra:
             raise ValueError("Spectra: channels must not repeat a name")
         self.names = chosen
         self.index = [self.all_names.index(c) for c in chosen]
-        self.H = H
-        self._ws: Dict[tuple, torch.Tensor] = {}      # (device, stream) -> workspace
         with torch.inference_mode(False):
             self._band_w = torch.from_numpy(self.band_w).to(self.device)
             self._band_wsum = torch.from_numpy(self.band_w.sum(axis=1)).to(self.device)
             self._chan = None if channels is None else torch.tensor(self.index, dtype=torch.int32, device=self.device)
             self.count = torch.zeros(self.n_leads, dtype=torch.float64, device=self.device)
         self.acc: Optional[torch.Tensor] = None       # [n_leads, Cs, R, K + 1, 3] once W is known (first update)
-        self.W: Optional[int] = None
 
     lat_weights_from = staticmethod(lat_weights_from)
 
@@ -177,31 +135,13 @@ class Spectra:
             self._tw = torch.from_numpy(twiddle_table(W)).to(self.device)
         self.W = W
 
-    def _check(self, lead, forecast, truth):
-        """argument checks of ``update``; returns (B, C, H, W)"""
-        if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < self.n_leads:
-            raise ValueError(f"Spectra.update: lead must be an integer in [0, {self.n_leads}), got {lead!r}")
-        C, H = len(self.all_names), self.H
-        for what, t in (("forecast", forecast), ("truth", truth)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 4:
-                raise ValueError(f"Spectra.update: {what} must be a [B, C, H, W] tensor")
-            if t.dtype != torch.float32:
-                raise ValueError(f"Spectra.update: {what} must be float32, got {t.dtype}")
-        B, Cf, Hf, W = forecast.shape
-        if (Cf, Hf) != (C, H) or W < 1:
-            raise ValueError(f"Spectra.update: forecast is {tuple(forecast.shape)}; the spectra have {C} channels "
-                             f"and {H} latitudes")
-        if truth.shape != forecast.shape:
-            raise ValueError(f"Spectra.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
+    def _check_longitudes(self, W: int) -> None:
         if self.W is not None and W != self.W:
             raise ValueError(f"Spectra.update: forecast has {W} longitudes, earlier updates had {self.W}")
         if schedule(W) is None:
             raise ValueError(f"Spectra.update: {W} longitudes are refused: W must be even and either a product of 2, 3 "
                              f"and 5 up to {_lib.lib.paradis_spectrum_fft_max_w()} or at most "
                              f"{_lib.lib.paradis_spectrum_direct_max_w()}")
-        dense_state(forecast, "forecast", "Spectra.update")
-        dense_state(truth, "truth", "Spectra.update")
-        return B, C, H, W
 
     def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor) -> None:
         B, C, H, W = self._check(lead, forecast, truth)
@@ -227,11 +167,7 @@ class Spectra:
     def result(self, sync_dist: bool = False) -> dict:
         if self.acc is None:
             raise RuntimeError("Spectra.result: no update yet - the number of longitudes is not known")
-        # (one tensor: the accumulators and, behind them, the counts - one all-reduce, one device read)
-        flat = sum_over_ranks(torch.cat([self.acc.reshape(-1), self.count]), sync_dist).numpy()
-        a = flat[:self.acc.numel()].reshape(tuple(self.acc.shape))
-        n = flat[self.acc.numel():].copy()
-        return report(a, n, self.names, self.bands)
+        return report(*read(self.acc, self.count, sync_dist), self.names, self.bands)
 
     @staticmethod
     def effective_resolution(result: dict, threshold: float = 0.5) -> np.ndarray:

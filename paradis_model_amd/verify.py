@@ -26,14 +26,15 @@ works on any device.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
-from ._tables import batch_stride, dense_state, sum_over_ranks, workspace
+from ._leadtable import LeadTable
+from ._tables import batch_stride, sum_over_ranks, workspace
 
 ACC_FIELDS = 8          # {n, sum se, sum e, sum ae, sum acc_b, n_acc, sum ff, sum tt}
 METRICS = ("rmse", "bias", "mae", "acc", "activity")
@@ -44,7 +45,7 @@ def lat_weights_from(loss) -> torch.Tensor:
     return loss.lat_weights_buf
 
 
-class Scorecard:
+class Scorecard(LeadTable):
     """Per-lead verification scores of a rollout, accumulated on the device (module docstring for the formulas).
 
     ``names``: the chunk's channel names (``PostSpec.names``); ``lat_weights``: ``[H]`` (any shape with H entries);
@@ -61,16 +62,13 @@ class Scorecard:
     all-reduce first (through the host under gloo, as ``Validator.result``).
     ``reset()`` clears the accumulators.  ``table(result, channels=None)``: a plain-text scorecard for logs."""
 
+    IT = NOUN = "the scorecard"
+    IT_HAS = HAS = "the scorecard has"
+    NEEDS = "a scorecard needs"
+
     def __init__(self, names: Sequence[str], lat_weights, n_leads: int, *, climatology: Optional[torch.Tensor] = None,
                  device="cuda"):
-        self.names = [str(n) for n in names]
-        C = len(self.names)
-        if C < 1:
-            raise ValueError("Scorecard: names must list at least one channel")
-        if isinstance(n_leads, bool) or int(n_leads) != n_leads or int(n_leads) < 1:
-            raise ValueError(f"Scorecard: n_leads must be an integer >= 1, got {n_leads!r}")
-        self.n_leads = int(n_leads)
-        self.device = torch.device(device)
+        super().__init__(names, n_leads, device)
         w = torch.as_tensor(lat_weights).detach().reshape(-1)
         if w.numel() < 1 or not w.is_floating_point():
             raise ValueError("Scorecard: lat_weights must be a floating-point vector [H]")
@@ -78,56 +76,13 @@ class Scorecard:
         if not bool(torch.isfinite(w64).all()) or bool((w64 < 0).any()) or float(w64.sum()) <= 0.0:
             raise ValueError("Scorecard: lat_weights must be finite, >= 0 and not all zero")
         self._wsum = float(w64.sum())                       # Z = W * sum_h w[h], in double on the host
+        self.H = w.numel()
         with torch.inference_mode(False):
             self.lat_w = w.to(device=self.device, dtype=torch.float32).contiguous().clone()
-            self.acc = torch.zeros(self.n_leads, C, ACC_FIELDS, dtype=torch.float64, device=self.device)
-        self.climatology = None
-        if climatology is not None:
-            cl = climatology
-            if not isinstance(cl, torch.Tensor) or cl.dim() != 4 or cl.dtype != torch.float32 or \
-                    cl.shape[0] < 1 or cl.shape[1] != C or cl.shape[2] != w.numel() or not cl.is_contiguous():
-                raise ValueError(f"Scorecard: climatology must be a contiguous float32 [K, {C}, {w.numel()}, W] tensor")
-            if cl.device != self.lat_w.device:
-                raise ValueError(f"Scorecard: climatology lives on {cl.device}, the scorecard on {self.lat_w.device}")
-            self.climatology = cl
-        self._ws: Dict[tuple, torch.Tensor] = {}      # (device, stream) -> workspace
-        self._slot0: Dict[int, torch.Tensor] = {}     # B -> zeros [B] int32: the index of a one-slot climatology
+            self.acc = torch.zeros(self.n_leads, self.C, ACC_FIELDS, dtype=torch.float64, device=self.device)
+        self._set_climatology(climatology, home=self.lat_w.device, same_index=True)
 
     lat_weights_from = staticmethod(lat_weights_from)
-
-    def _check(self, lead, forecast, truth, clim_index):
-        """argument checks of ``update``; returns (B, C, H, W)"""
-        if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < self.n_leads:
-            raise ValueError(f"Scorecard.update: lead must be an integer in [0, {self.n_leads}), got {lead!r}")
-        C, H = len(self.names), self.lat_w.numel()
-        for what, t in (("forecast", forecast), ("truth", truth)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 4:
-                raise ValueError(f"Scorecard.update: {what} must be a [B, C, H, W] tensor")
-            if t.dtype != torch.float32:
-                raise ValueError(f"Scorecard.update: {what} must be float32, got {t.dtype}")
-        B, Cf, Hf, W = forecast.shape
-        if (Cf, Hf) != (C, H) or W < 1:
-            raise ValueError(f"Scorecard.update: forecast is {tuple(forecast.shape)}; the scorecard has {C} channels "
-                             f"and {H} latitudes")
-        if truth.shape != forecast.shape:
-            raise ValueError(f"Scorecard.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
-        dense_state(forecast, "forecast", "Scorecard.update")
-        dense_state(truth, "truth", "Scorecard.update")
-        if self.climatology is None:
-            if clim_index is not None:
-                raise ValueError("Scorecard.update: clim_index given, but the scorecard has no climatology")
-        else:
-            if self.climatology.shape[3] != W:
-                raise ValueError(f"Scorecard.update: forecast has {W} longitudes, the climatology "
-                                 f"{self.climatology.shape[3]}")
-            if clim_index is None:
-                if self.climatology.shape[0] != 1:
-                    raise ValueError(f"Scorecard.update: clim_index is needed to choose among the "
-                                     f"{self.climatology.shape[0]} climatology slots")
-            elif not isinstance(clim_index, torch.Tensor) or clim_index.dtype != torch.int32 or \
-                    tuple(clim_index.shape) != (B,):
-                raise ValueError(f"Scorecard.update: clim_index must be an int32 tensor [{B}]")
-        return B, C, H, W
 
     def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
                clim_index: Optional[torch.Tensor] = None) -> None:
@@ -136,23 +91,14 @@ class Scorecard:
         if B == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
             return
         clim = self.climatology
-        if clim is not None:
-            if clim_index is None:
-                if B not in self._slot0:
-                    with torch.inference_mode(False):
-                        self._slot0[B] = torch.zeros(B, dtype=torch.int32, device=forecast.device)
-                clim_index = self._slot0[B]
-            if not clim_index.is_cuda:
-                raise ValueError("Scorecard.update: clim_index must live on the device")
-            clim_index = clim_index.contiguous()         # a column of [B, n_stored] becomes dense; no host wait
+        clim_index, K = self._clim_args(clim_index, forecast)
         P = H * W
         with_clim = clim is not None
         ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_verify_ws_bytes(B, C, H, W, int(with_clim))))
         _lib.call("verify_update", (12.0 if with_clim else 8.0) * B * C * P, dptr(forecast),
                   batch_stride(forecast, C * P), dptr(truth), batch_stride(truth, C * P), dptr(clim),
-                  dptr(clim_index) if with_clim else None, clim.shape[0] if with_clim else 0,
-                  dptr(self.lat_w), float(W) * self._wsum, dptr(self.acc[int(lead)]), dptr(ws), B, C, H, W,
-                  stream_ptr())
+                  dptr(clim_index), K, dptr(self.lat_w), float(W) * self._wsum, dptr(self.acc[int(lead)]), dptr(ws),
+                  B, C, H, W, stream_ptr())
 
     def reset(self) -> None:
         self.acc.zero_()

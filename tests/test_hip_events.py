@@ -159,7 +159,9 @@ def test_counts_at_grid_edges(case):
 SOURCE_CASES = [("plain", ("plain",), None, "ge"), ("speed", ("speed",), None, "ge"), ("anomaly", ("anomaly",), None, "ge"),
                 ("all three", ("plain", "speed", "anomaly"), None, "ge"), ("T=1", ("plain",), [0.25], "ge"),
                 ("T=2", ("plain", "anomaly"), [0.25, -0.5], "ge"), ("T=8 unsorted", ("plain", "anomaly"), THR8, "ge"),
-                ("le", ("plain", "speed", "anomaly"), None, "le")]
+                ("le", ("plain", "speed", "anomaly"), None, "le"),
+                # (thresholds rounded up to a compiled variant: 3 -> 4 and 5 -> 8, the rest padded with NaN)
+                ("T=3", ("plain", "speed"), [0.25, -0.5, 1.0], "ge"), ("T=5", ("plain", "anomaly"), THR8[:5], "le")]
 
 
 @pytest.mark.parametrize("H,W", [(32, 64), (6, 1440)])

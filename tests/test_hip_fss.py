@@ -100,7 +100,10 @@ SOURCE_CASES = [("plain", ("plain",), None, "ge", SCALES), ("speed", ("speed",),
                 ("T=3", ("plain", "anomaly"), [0.25, -0.5, 1.25], "ge", SCALES),
                 ("T=8 unsorted", ("plain", "anomaly"), THR8, "ge", SCALES),
                 ("le", ("plain", "speed", "anomaly"), None, "le", SCALES), ("K=1", ("plain", "speed"), None, "ge", [3]),
-                ("K=max", ("plain", "anomaly"), THR8, "ge", [0, 1, 2, 3, 4, 6, 9, NY_MAX][:K_MAX])]
+                ("K=max", ("plain", "anomaly"), THR8, "ge", [0, 1, 2, 3, 4, 6, 9, NY_MAX][:K_MAX]),
+                # (test_hip_events.py's "T=3" and "T=5": threshold counts that events.hip rounds up to a compiled variant)
+                ("T=3 speed", ("plain", "speed"), [0.25, -0.5, 1.0], "ge", SCALES),
+                ("T=5", ("plain", "anomaly"), THR8[:5], "le", SCALES)]
 
 
 @pytest.mark.parametrize("H,W", [(32, 64), (6, 1440)])
@@ -159,7 +162,7 @@ def test_non_finite_cells_are_non_events(bad):
 # ================================================================================================ 3. against events.hip
 @pytest.mark.parametrize("H,W", [(32, 64), (6, 1440), (17, 37)])
 def test_scale_zero_equals_the_event_table_on_the_device(H, W):
-    """the restated source evaluation gives events.hip's bits: nV, nF, nO are EventTable's, and at ny = nx = 0
+    """the shared source evaluation (event_source.h) gives the same bits in both kernels: nV, nF, nO are EventTable's, and at ny = nx = 0
     FF == nF, OO == nO, FO == nFO"""
     f, t, clim = design(41, 3, H, W, K=2)
     ev, srcs = make_sources(("plain", "speed", "anomaly"))
