@@ -808,6 +808,44 @@ int paradis_fss_update(const float* fc, int64_t fc_bs, const float* truth, int64
                        const int* half_y, const int* half_x, int64_t* acc_lead, int64_t* n_samples_lead, void* ws,
                        int B, int C, int S, int H, int W, int K, void* stream);
 
+/* ---- Ensemble verification (ABI 10, additive), csrc/ensemble.hip: per lead, chosen channel and latitude row the row
+ * sums of the CRPS and spread / skill terms of M-member ensembles and the histogram of the truth's rank.  The project's
+ * own textbook definitions in the spirit of WeatherBench-2's probabilistic metrics; not pinned against any package.  One
+ * launch pair on `stream`, no host synchronisation, no memset or copy nodes, no atomics, no sort; neither input is
+ * written.
+ *   fc [G * M, C, H, W] fp32 in physical units, member-minor (member i of ensemble g is batch entry g M + i), dense
+ *   [C, H, W] states, fc_bs the stride between members in elements; truth [G, C, H, W], truth_bs the stride between
+ *   ensembles; 2 <= M <= paradis_ens_max_members();
+ *   chan int32 [Cs] (DEVICE): the state channel of output channel cs - only these planes are read; an entry outside
+ *   [0, C) is not read, adds 0 to its counters and turns its four sums into NaN;
+ *   rM = 1.0f / M formed by the caller; salt: uint32, the caller's seed + lead.
+ * A cell is valid iff its truth y and all M member values x_i are finite; an invalid cell adds nothing anywhere.  Per
+ * valid cell, in fp32, uncontracted, in exactly this order:
+ *   A = sum_i |x_i - y| (i ascending, from 0.0f)      P = sum_{i<j} |x_i - x_j| (i ascending, then j ascending)
+ *   m = (sum_i x_i) * rM      E2 = (m - y) * (m - y)      V = sum_i (x_i - m) * (x_i - m)
+ *   lo = #{x_i < y}   eq = #{x_i == y}   r = lo + hash32(key) % (eq + 1), the truth's rank in 0 .. M
+ *   key = uint32(((n C + c) H + h) W + w) + salt * 0x9E3779B9 (mod 2^32), c = chan[cs], n = n_samples_lead[0] as the
+ *   call finds it + g;  hash32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *   acc_real_lead: DEVICE double [Cs][H][4], the rows of this lead: {sum A, sum P, sum E2, sum V} over the row's valid
+ *   cells, each cell term widened to double before it meets another, summed in a fixed order; the ensembles are folded
+ *   in g order, (acc + s_0) + s_1 ..: two calls give the bits of one call of the concatenated ensembles;
+ *   acc_int_lead: DEVICE int64 [Cs][H][2 + M]: {nV, hist[0 .. M]} += the valid cells and the histogram of r (exact);
+ *   n_samples_lead: DEVICE int64 [1] += G, read by the counting kernel before the finishing kernel adds to it.
+ *   Ordinary read-modify-writes (calls on one stream are ordered).
+ * A workgroup owns paradis_ens_rows(W, M) (>= 4; 0 for W < 1 or M outside its range) whole rows of one (ensemble,
+ * channel).  ws: paradis_ens_ws_bytes(G, Cs, H, W, M) bytes, 8-byte aligned: double [G][Cs][H][4], then uint32
+ * [G][Cs][H][2 + M].  G == 0 does nothing.  rc 1 before any HIP call for: G < 0, C / Cs / H / W < 1, M outside its range,
+ * a NULL accumulator, ws or input, H W >= 2^31 - 8192, batch strides shorter than a state, a grid above the launch limit.
+ * W % 4 == 0 with 16-byte aligned bases and strides takes one 16-byte load per plane and quad of cells (8-byte loads of
+ * cell pairs above 16 members), anything else scalar loads: the same bits.
+ * Algorithmic HBM bytes per cell of a channel: 4 (M + 1). */
+int paradis_ens_max_members(void);
+int paradis_ens_rows(int W, int M);
+size_t paradis_ens_ws_bytes(int G, int Cs, int H, int W, int M);
+int paradis_ens_update(const float* fc, int64_t fc_bs, const float* truth, int64_t truth_bs, const int* chan, float rM,
+                       unsigned salt, double* acc_real_lead, int64_t* acc_int_lead, int64_t* n_samples_lead, void* ws,
+                       int G, int M, int C, int Cs, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

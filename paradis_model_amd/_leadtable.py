@@ -1,6 +1,6 @@
-"""What the per-lead verification tables share - ``verify.Scorecard``, ``spectrum.Spectra``, ``events.EventTable`` and
-``neighbourhood.FractionsTable``: the argument checks of their constructors and of ``update``, the one-slot climatology
-index and the single device read of ``result``.
+"""What the per-lead verification tables share - ``verify.Scorecard``, ``spectrum.Spectra``, ``events.EventTable``,
+``neighbourhood.FractionsTable`` and ``ensemble.EnsembleCard``: the argument checks of their constructors and of
+``update``, the one-slot climatology index and the single device read of ``result``.
 
 Plain functions first; ``who`` is the class name that opens every message, so each table keeps its own words.  The small
 base class ``LeadTable`` holds what the checks need (``names``, ``C``, ``n_leads``, ``device``, ``H``, ``W``, ``bands``,
@@ -94,10 +94,11 @@ def climatology_tensor(who: str, it: str, cl, C: int, H: int, W: Optional[int], 
     return cl
 
 
-def check_states(who: str, it_has: str, n_leads: int, C: int, H: int, lead, forecast, truth,
-                 n_lon: Optional[int] = None) -> Tuple[int, int]:
-    """the lead and the two ``[B, C, H, W]`` fp32 tensors of ``update`` against a table of ``C`` channels, ``H``
-    latitudes and - where the table was made for them - ``n_lon`` longitudes; returns ``(B, W)``"""
+def check_lead_and_forecast(who: str, it_has: str, n_leads: int, C: int, H: int, lead, forecast, truth,
+                            n_lon: Optional[int] = None) -> Tuple[int, int]:
+    """the lead, both tensors' rank and dtype and the forecast's shape ``[B, C, H, W]`` against a table of ``C``
+    channels, ``H`` latitudes and - where the table was made for them - ``n_lon`` longitudes; returns ``(B, W)``.  What
+    the truth's shape must be is the caller's: ``check_states`` or ``check_member_states``"""
     if isinstance(lead, bool) or not isinstance(lead, (int, np.integer)) or not 0 <= int(lead) < n_leads:
         raise ValueError(f"{who}.update: lead must be an integer in [0, {n_leads}), got {lead!r}")
     for what, t in (("forecast", forecast), ("truth", truth)):
@@ -113,9 +114,31 @@ def check_states(who: str, it_has: str, n_leads: int, C: int, H: int, lead, fore
     elif (Cf, Hf, W) != (C, H, n_lon):
         raise ValueError(f"{who}.update: forecast is {tuple(forecast.shape)}; {it_has} {C} channels, "
                          f"{H} latitudes and {n_lon} longitudes")
+    return B, W
+
+
+def check_states(who: str, it_has: str, n_leads: int, C: int, H: int, lead, forecast, truth,
+                 n_lon: Optional[int] = None) -> Tuple[int, int]:
+    """the lead and the two ``[B, C, H, W]`` fp32 tensors of ``update`` against a table of ``C`` channels, ``H``
+    latitudes and - where the table was made for them - ``n_lon`` longitudes; returns ``(B, W)``"""
+    B, W = check_lead_and_forecast(who, it_has, n_leads, C, H, lead, forecast, truth, n_lon)
     if truth.shape != forecast.shape:
         raise ValueError(f"{who}.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}")
     return B, W
+
+
+def check_member_states(who: str, it_has: str, n_leads: int, C: int, H: int, members: int, lead, forecast,
+                        truth) -> Tuple[int, int]:
+    """``check_states`` for a table of ensembles: forecast ``[G * members, C, H, W]``, member-minor, and ONE truth per
+    ensemble, ``[G, C, H, W]``; returns ``(G, W)``"""
+    B, W = check_lead_and_forecast(who, it_has, n_leads, C, H, lead, forecast, truth)
+    if B % members != 0:
+        raise ValueError(f"{who}.update: forecast is {tuple(forecast.shape)}: {B} states are not whole ensembles of "
+                         f"{members} members")
+    if tuple(truth.shape) != (B // members, C, H, W):
+        raise ValueError(f"{who}.update: truth is {tuple(truth.shape)}, forecast {tuple(forecast.shape)}: "
+                         f"{B // members} ensembles of {members} members need truth {(B // members, C, H, W)}")
+    return B // members, W
 
 
 def check_clim_index(who: str, it_has: str, climatology, clim_index, B: int, W: int) -> None:
@@ -167,7 +190,7 @@ class LeadTable:
     def __init__(self, names: Sequence[str], n_leads: int, device):
         self.who = type(self).__name__
         self.names, self.n_leads = names_and_leads(self.who, names, n_leads)
-        self.all_names = self.names                   # the channels of a state (Spectra narrows ``names`` to its subset)
+        self.all_names = self.names                   # the channels of a state (``_set_channels`` narrows ``names``)
         self.C = len(self.names)
         self.device = torch.device(device)
         self.H: Optional[int] = None
@@ -182,6 +205,20 @@ class LeadTable:
         self.H = lat.size
         self.bands, self.band_w = bands_to_weights(self.who, lat, row_weights(self.who, lat, weights), bands)
         return lat
+
+    def _set_channels(self, channels) -> None:
+        """``names`` narrowed to the subset ``channels`` (by name, in the order given; None: all) and ``index``, their
+        positions in a state; ``all_names`` stays the state's names"""
+        chosen = self.all_names if channels is None else [str(c) for c in channels]
+        if len(chosen) < 1:
+            raise ValueError(f"{self.who}: channels must name at least one channel")
+        for c in chosen:
+            if c not in self.all_names:
+                raise ValueError(f"{self.who}: channel '{c}' is not among the names")
+        if len(set(chosen)) != len(chosen):
+            raise ValueError(f"{self.who}: channels must not repeat a name")
+        self.names = chosen
+        self.index = [self.all_names.index(c) for c in chosen]
 
     def _set_climatology(self, climatology, home=None, same_index: bool = False) -> None:
         if climatology is not None:

@@ -156,6 +156,10 @@ SIGNATURES = {
     "paradis_fss_rows": (I, [I, I]),
     "paradis_fss_ws_bytes": (S, [I, I, I, I, I]),
     "paradis_fss_update": (I, [P, L, P, L, P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "paradis_ens_max_members": (I, []),
+    "paradis_ens_rows": (I, [I, I]),
+    "paradis_ens_ws_bytes": (S, [I, I, I, I, I]),
+    "paradis_ens_update": (I, [P, L, P, L, P, F, ctypes.c_uint, P, P, P, P, I, I, I, I, I, I, P]),
 }
 
 _missing = []

@@ -85,8 +85,6 @@ inline int event_sources_fill(const char* who, SourceInputs& in, bool& vec, cons
   return 0;
 }
 
-__device__ __forceinline__ unsigned count_lanes(bool p) { return (unsigned)__popcll(__ballot(p)); }
-
 // the planes of one source for one sample; f1 / t1: the second component of a speed source; cl: the climatology plane,
 // which the caller sets once it has tested the sample's slot
 struct SourcePlanes {

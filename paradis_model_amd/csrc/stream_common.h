@@ -32,6 +32,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// the lanes of the wave for which p holds: the integer counting of events.hip, fss.hip and ensemble.hip
+__device__ __forceinline__ unsigned count_lanes(bool p) { return (unsigned)__popcll(__ballot(p)); }
+
 // the four waves of a 256-thread workgroup: s[j] is this wave's sum j (after the xor tree); thread j < NS gets the
 // workgroup's sum j handed to store(j, sum)
 template <class T, int NS, class Store>

@@ -208,10 +208,10 @@ def chunk_plan(forecast_steps: int, output_frequency: int, write_every_n: Option
 
 
 # ---------------------------------------------------------------------------------- the predict loop
-def _passed(scorecard, spectra, events, fractions) -> list:
+def _passed(scorecard, spectra, events, fractions, ensemble=None) -> list:
     """the verification tables given to ``run`` (``_leadtable.LeadTable``: each brings its phrases and whether its
     ``update`` takes ``clim_index``), in the order of their refusals and of their launches"""
-    return [t for t in (scorecard, spectra, events, fractions) if t is not None]
+    return [t for t in (scorecard, spectra, events, fractions, ensemble) if t is not None]
 
 
 class Forecaster:
@@ -250,6 +250,14 @@ class Forecaster:
     at lead ``k`` (three more launches on the main stream, right after the others and in front of the same event).
     The refusals are the event table's.
 
+    ``run(..., ensemble=<ensemble.EnsembleCard>, truth=..., truth_normalized=False)``: beside or without the others, a
+    batch of ``B = G * members`` states is scored as ``G`` ensembles, member-minor (member ``i`` of ensemble ``g`` is
+    batch entry ``g * members + i``).  ``truth`` keeps its shape ``[B, n_stored, C, H, W]``; the card is updated with
+    the finished state and ``t[::members]``, the truth of each ensemble's FIRST member: the members of one ensemble
+    share their truth, the other members' truth entries are not read by the card.  The card launches last (one more
+    launch pair on the main stream, after ``fractions`` and in front of the same event).  The refusals are the
+    scorecard's, and a ``B`` that is no multiple of ``members``.
+
     ``run(..., encoder=<encode.EncodeSpec>, init=<(state [B, 1, C, H, W], dew [B, 1, L, H, W] or None) or None>)``: a
     flushed chunk is regrouped into the writer's named variables and BitRounded on the device (``encode.encode_chunk``,
     one launch on the main stream) into a ring of its own, which is handed over in place of the plain chunk, with the
@@ -283,11 +291,12 @@ class Forecaster:
         return ring.pin() if pinned else ring
 
     def _check_verification(self, scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W, spectra=None,
-                            events=None, fractions=None):
-        """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=...)``, before the rollout starts;
+                            events=None, fractions=None, ensemble=None):
+        """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=..., ensemble=...)``, before the rollout
+        starts;
         returns the forecaster's ``[B, 1, C, H, W]`` scratch tensor for a model-space truth (``truth_normalized=True``),
         else None"""
-        tables = _passed(scorecard, spectra, events, fractions)
+        tables = _passed(scorecard, spectra, events, fractions, ensemble)
         if not tables:
             if truth is not None or clim_index is not None or truth_normalized:
                 raise ValueError("Forecaster.run: truth, truth_normalized and clim_index go with a scorecard")
@@ -302,6 +311,9 @@ class Forecaster:
                 raise ValueError(f"Forecaster.run: {t.HAS} {t.n_leads} leads, the rollout stores {n_stored}")
             if list(t.all_names) != list(self.spec.names):
                 raise ValueError(f"Forecaster.run: {t.NOUN}'s names are not the chunk's channel names (PostSpec.names)")
+        if ensemble is not None and B % ensemble.members != 0:
+            raise ValueError(f"Forecaster.run: the ensemble card has {ensemble.members} members, a batch of {B} states "
+                             f"is not whole ensembles")
         if clim_index is not None and (clim_index.dtype != torch.int32 or tuple(clim_index.shape) != (B, n_stored)):
             raise ValueError(f"Forecaster.run: clim_index must be int32 {(B, n_stored)}, got {clim_index.dtype} "
                              f"{tuple(clim_index.shape)}")
@@ -342,8 +354,8 @@ class Forecaster:
     def run(self, input_data, forcings, constants, on_chunk: Optional[Callable],
             forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
             truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None, encoder=None, init=None,
-            spectra=None, events=None, fractions=None):
-        tables = _passed(scorecard, spectra, events, fractions)
+            spectra=None, events=None, fractions=None, ensemble=None):
+        tables = _passed(scorecard, spectra, events, fractions, ensemble)
         for t in tables:                                     # (host-side refusals, in front of the device checks)
             if truth is None:
                 raise ValueError(f"Forecaster.run: {t.NEEDS} truth [B, n_stored, C, H, W] on the device")
@@ -356,7 +368,7 @@ class Forecaster:
         B, _, _, H, W = input_data.shape
         C, L = self.spec.num_channels, self.spec.num_levels
         truth_phys = self._check_verification(scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W,
-                                              spectra, events, fractions)
+                                              spectra, events, fractions, ensemble)
         init = self._check_encoder(encoder, init, B, C, L, H, W)
         sizes = [p.flush[1] for p in plan if p.flush is not None]         # per chunk its number of states
         n_chunk, sizes = max(sizes), iter(sizes)
@@ -391,8 +403,11 @@ class Forecaster:
                         postprocess(t, self.spec, self.lat_deg, self.lon_deg, truth_phys, 0)
                         t = truth_phys[:, 0]
                     k = None if clim_index is None else clim_index[:, i_stored]
-                    for table in tables:                   # (scorecard, spectra, events, fractions: the launch order)
-                        table.update(i_stored, d[:, p.slot], t, *((k,) if table.TAKES_CLIM_INDEX else ()))
+                    for table in tables:         # (scorecard, spectra, events, fractions, ensemble: the launch order)
+                        if table is ensemble:              # one truth per ensemble: its first member's
+                            table.update(i_stored, d[:, p.slot], t[::ensemble.members])
+                        else:
+                            table.update(i_stored, d[:, p.slot], t, *((k,) if table.TAKES_CLIM_INDEX else ()))
                 i_stored += 1
             if p.flush is not None:
                 start, n = p.flush

@@ -99,16 +99,7 @@ class Spectra(LeadTable):
                  channels: Optional[Sequence[str]] = None, device="cuda"):
         super().__init__(names, n_leads, device)
         self._set_grid(lat_deg, weights, bands)
-        chosen = self.all_names if channels is None else [str(c) for c in channels]
-        if len(chosen) < 1:
-            raise ValueError("Spectra: channels must name at least one channel")
-        for c in chosen:
-            if c not in self.all_names:
-                raise ValueError(f"Spectra: channel '{c}' is not among the names")
-        if len(set(chosen)) != len(chosen):
-            raise ValueError("Spectra: channels must not repeat a name")
-        self.names = chosen
-        self.index = [self.all_names.index(c) for c in chosen]
+        self._set_channels(channels)
         with torch.inference_mode(False):
             self._band_w = torch.from_numpy(self.band_w).to(self.device)
             self._band_wsum = torch.from_numpy(self.band_w.sum(axis=1)).to(self.device)
