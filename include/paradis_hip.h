@@ -846,6 +846,46 @@ int paradis_ens_update(const float* fc, int64_t fc_bs, const float* truth, int64
                        unsigned salt, double* acc_real_lead, int64_t* acc_int_lead, int64_t* n_samples_lead, void* ws,
                        int G, int M, int C, int Cs, int H, int W, void* stream);
 
+/* ---- Probabilistic event verification (ABI 10, additive), csrc/probability.hip: per lead, event source, latitude row
+ * and threshold the joint integer histogram of (the truth has the event, the number of members that have it) of M-member
+ * ensembles - what the Brier score and its decomposition, the reliability diagram and the ROC curve are made of.  The
+ * project's own textbook definitions; not pinned against any package.  One launch pair on `stream`, no host
+ * synchronisation, no memset or copy nodes, no global atomics, no float arithmetic after the decision: the counts are
+ * exact; neither input is written.
+ *   fc [G * M, C, H, W] fp32 in physical units, member-minor (member i of ensemble g is batch entry g M + i), dense
+ *   [C, H, W] states, fc_bs the stride between members in elements; truth [G, C, H, W], truth_bs the stride between
+ *   ensembles; 2 <= M <= paradis_prob_max_members();
+ *   clim [K, C, H, W] fp32 dense and clim_index [G] int32 (DEVICE), one slot per ensemble, or both NULL;
+ *   src_table, thr_table: HOST tables as paradis_events_update's, with its limits (paradis_events_max_sources(),
+ *   paradis_events_max_thresholds() = TMAX) and its checks; T in 1 .. TMAX: the thresholds an accumulator row has room
+ *   for, at least every source's nthr.  The value of a source and the decision sign * x >= thr'[j] are those of
+ *   paradis_events_update (csrc/event_source.h), for the truth and for each member.
+ * A cell is valid for a source iff every value it reads is finite (the truth's channel or channels, the climatology cell
+ * of an anomaly, the channel or channels of all M members); an ensemble whose clim_index is outside [0, K) has no valid
+ * cell for anomaly sources and nothing of that slot is read.  Invalid cells are counted nowhere.  Per valid cell and
+ * threshold j < nthr, o = the truth has the event (0 / 1), k = the members that have it (0 .. M).
+ *   acc_lead: DEVICE int64 [S][H][paradis_prob_counters(M, T)], the row of this lead, counters = 1 + 2 T (M + 1):
+ *     [0] nV      [1 + (2 j + o) (M + 1) + k] joint[j][o][k]
+ *   each += the counts of this call (entries of j >= nthr: += 0); sum_{o,k} joint[j][o][k] == nV for every j < nthr;
+ *   n_samples_lead: DEVICE int64 [1] += G.  Ordinary read-modify-writes (calls on one stream are ordered); the ensembles
+ *   are folded in g order.
+ * A workgroup owns paradis_prob_rows(W) ~ 1024 / W (a multiple of 4, >= 4; 0 for W < 1) whole rows of one (ensemble,
+ * source) and a wave whole rows; the members are streamed with a runtime bound (one compiled kernel for every M), a row's counts are kept
+ * in a per-wave LDS histogram.  ws: paradis_prob_ws_bytes(G, S, H, W, M, T) bytes, 4-byte aligned: uint32
+ * [G][S][H][counters]; 0, like paradis_prob_counters, for an M or T outside its range or an empty shape.
+ * G == 0 does nothing.  rc 1 before any HIP call for everything paradis_events_update refuses (B there is G), M or T
+ * outside its range, a source with more than T thresholds, a NULL acc_lead, n_samples_lead, ws, input or table.
+ * W % 4 == 0 with 16-byte aligned bases and strides takes 16-byte loads, anything else scalar loads: the same counts.
+ * Algorithmic HBM bytes per cell of a source: 4 (M + 1) plain, 8 (M + 1) speed, 4 (M + 1) + 4 anomaly. */
+int paradis_prob_max_members(void);
+int paradis_prob_rows(int W);
+int paradis_prob_counters(int M, int T);
+size_t paradis_prob_ws_bytes(int G, int S, int H, int W, int M, int T);
+int paradis_prob_update(const float* fc, int64_t fc_bs, const float* truth, int64_t truth_bs, const float* clim,
+                        const int* clim_index, int K, const int* src_table, const float* thr_table, int64_t* acc_lead,
+                        int64_t* n_samples_lead, void* ws, int G, int M, int T, int C, int S, int H, int W,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

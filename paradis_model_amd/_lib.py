@@ -160,6 +160,11 @@ SIGNATURES = {
     "paradis_ens_rows": (I, [I, I]),
     "paradis_ens_ws_bytes": (S, [I, I, I, I, I]),
     "paradis_ens_update": (I, [P, L, P, L, P, F, ctypes.c_uint, P, P, P, P, I, I, I, I, I, I, P]),
+    "paradis_prob_max_members": (I, []),
+    "paradis_prob_rows": (I, [I]),
+    "paradis_prob_counters": (I, [I, I]),
+    "paradis_prob_ws_bytes": (S, [I, I, I, I, I, I]),
+    "paradis_prob_update": (I, [P, L, P, L, P, P, I, P, P, P, P, P, I, I, I, I, I, I, I, P]),
 }
 
 _missing = []

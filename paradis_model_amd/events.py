@@ -167,7 +167,9 @@ class EventLeadTable(LeadTable):
     """What ``EventTable`` and ``neighbourhood.FractionsTable`` share: construction up to ``parse_events``, the int64
     accumulator rows that begin ``{nV, nF[TMAX], nO[TMAX]}`` and ``n_samples``, and the parts of ``counts`` / ``result``
     that read them.  ``n_lon``: the number of longitudes where the constructor knows it; ``row``: the int64 entries of
-    one accumulator row, given ``tmax``."""
+    one accumulator row, given ``tmax``.  ``probability.ProbabilityTable`` sits on it too, with rows of its own
+    (``{nV, joint[T][2][M + 1]}``): it takes the construction, ``reset``, ``_dead`` and ``_finish`` and leaves
+    ``_counts_head`` / ``_past`` alone."""
     IT = "the table"
     IT_HAS = "the table has"
 

@@ -208,10 +208,10 @@ def chunk_plan(forecast_steps: int, output_frequency: int, write_every_n: Option
 
 
 # ---------------------------------------------------------------------------------- the predict loop
-def _passed(scorecard, spectra, events, fractions, ensemble=None) -> list:
+def _passed(scorecard, spectra, events, fractions, ensemble=None, probability=None) -> list:
     """the verification tables given to ``run`` (``_leadtable.LeadTable``: each brings its phrases and whether its
     ``update`` takes ``clim_index``), in the order of their refusals and of their launches"""
-    return [t for t in (scorecard, spectra, events, fractions, ensemble) if t is not None]
+    return [t for t in (scorecard, spectra, events, fractions, ensemble, probability) if t is not None]
 
 
 class Forecaster:
@@ -258,6 +258,12 @@ class Forecaster:
     launch pair on the main stream, after ``fractions`` and in front of the same event).  The refusals are the
     scorecard's, and a ``B`` that is no multiple of ``members``.
 
+    ``run(..., probability=<probability.ProbabilityTable>, truth=..., truth_normalized=False, clim_index=...)``: beside
+    or without the others, the same member-minor batch as for ``ensemble`` goes through ``probability.update`` at lead
+    ``k`` with ``t[::members]`` and ``clim_index[::members, k]`` - the truth and the climatology slot of each ensemble's
+    FIRST member.  The table launches after ``ensemble`` (one more launch pair on the main stream, in front of the same
+    event).  The refusals are the ensemble card's.
+
     ``run(..., encoder=<encode.EncodeSpec>, init=<(state [B, 1, C, H, W], dew [B, 1, L, H, W] or None) or None>)``: a
     flushed chunk is regrouped into the writer's named variables and BitRounded on the device (``encode.encode_chunk``,
     one launch on the main stream) into a ring of its own, which is handed over in place of the plain chunk, with the
@@ -291,12 +297,12 @@ class Forecaster:
         return ring.pin() if pinned else ring
 
     def _check_verification(self, scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W, spectra=None,
-                            events=None, fractions=None, ensemble=None):
-        """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=..., ensemble=...)``, before the rollout
-        starts;
+                            events=None, fractions=None, ensemble=None, probability=None):
+        """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=..., ensemble=..., probability=...)``,
+        before the rollout starts;
         returns the forecaster's ``[B, 1, C, H, W]`` scratch tensor for a model-space truth (``truth_normalized=True``),
         else None"""
-        tables = _passed(scorecard, spectra, events, fractions, ensemble)
+        tables = _passed(scorecard, spectra, events, fractions, ensemble, probability)
         if not tables:
             if truth is not None or clim_index is not None or truth_normalized:
                 raise ValueError("Forecaster.run: truth, truth_normalized and clim_index go with a scorecard")
@@ -314,6 +320,9 @@ class Forecaster:
         if ensemble is not None and B % ensemble.members != 0:
             raise ValueError(f"Forecaster.run: the ensemble card has {ensemble.members} members, a batch of {B} states "
                              f"is not whole ensembles")
+        if probability is not None and B % probability.members != 0:
+            raise ValueError(f"Forecaster.run: the probability table has {probability.members} members, a batch of {B} "
+                             f"states is not whole ensembles")
         if clim_index is not None and (clim_index.dtype != torch.int32 or tuple(clim_index.shape) != (B, n_stored)):
             raise ValueError(f"Forecaster.run: clim_index must be int32 {(B, n_stored)}, got {clim_index.dtype} "
                              f"{tuple(clim_index.shape)}")
@@ -354,8 +363,8 @@ class Forecaster:
     def run(self, input_data, forcings, constants, on_chunk: Optional[Callable],
             forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
             truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None, encoder=None, init=None,
-            spectra=None, events=None, fractions=None, ensemble=None):
-        tables = _passed(scorecard, spectra, events, fractions, ensemble)
+            spectra=None, events=None, fractions=None, ensemble=None, probability=None):
+        tables = _passed(scorecard, spectra, events, fractions, ensemble, probability)
         for t in tables:                                     # (host-side refusals, in front of the device checks)
             if truth is None:
                 raise ValueError(f"Forecaster.run: {t.NEEDS} truth [B, n_stored, C, H, W] on the device")
@@ -368,7 +377,7 @@ class Forecaster:
         B, _, _, H, W = input_data.shape
         C, L = self.spec.num_channels, self.spec.num_levels
         truth_phys = self._check_verification(scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W,
-                                              spectra, events, fractions, ensemble)
+                                              spectra, events, fractions, ensemble, probability)
         init = self._check_encoder(encoder, init, B, C, L, H, W)
         sizes = [p.flush[1] for p in plan if p.flush is not None]         # per chunk its number of states
         n_chunk, sizes = max(sizes), iter(sizes)
@@ -403,9 +412,12 @@ class Forecaster:
                         postprocess(t, self.spec, self.lat_deg, self.lon_deg, truth_phys, 0)
                         t = truth_phys[:, 0]
                     k = None if clim_index is None else clim_index[:, i_stored]
-                    for table in tables:         # (scorecard, spectra, events, fractions, ensemble: the launch order)
+                    for table in tables:         # (scorecard, .., fractions, ensemble, probability: the launch order)
                         if table is ensemble:              # one truth per ensemble: its first member's
                             table.update(i_stored, d[:, p.slot], t[::ensemble.members])
+                        elif table is probability:         # and one climatology slot: the members share their valid time
+                            m = probability.members
+                            table.update(i_stored, d[:, p.slot], t[::m], *(() if k is None else (k[::m],)))
                         else:
                             table.update(i_stored, d[:, p.slot], t, *((k,) if table.TAKES_CLIM_INDEX else ()))
                 i_stored += 1
