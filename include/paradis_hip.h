@@ -704,6 +704,37 @@ int paradis_spherical_winds_inplace(float* data, const int* units, const int* un
                                     const double* plev, int n_levels, const double* trig, int K, int C, int H, int W,
                                     void* stream);
 
+/* ---- The quantile climatology of a device-resident store (ABI 10, additive), csrc/quantile.hip: per slot, channel and
+ * cell the quantiles of the rows that a slot's list names - per-cell thresholds for the event tables (an anomaly source
+ * against a quantile field at threshold 0 decides x >= q).  The project's own definition; not pinned against any package.
+ *
+ * Store, ptr, rows, cols and flag as paradis_clim_mean takes them (no weights: quantiles are unweighted).  For slot k,
+ * channel c and cell p: the values x[rows[j], cols[c], p], j in [ptr[k], ptr[k + 1]), -0.0 read as +0.0, NaN and +-Inf
+ * skipped; m of them are kept, v[0] <= .. <= v[m-1] ascending.  For each of the Q levels q_host[i] in [0, 1] (HOST
+ * doubles, Q <= 8, checked on the host and passed as kernel arguments):
+ *   pos = q * (m - 1),  lo = floor(pos),  hi = min(lo + 1, m - 1),  frac = pos - lo
+ *   out[i, k, c, p] = (float)(v[lo] + (v[hi] - v[lo]) * frac)     in double, uncontracted, one rounding
+ *   out[i, k, c, p] = NaN when m < min_count (min_count >= 1)
+ * numpy's method="linear" position rule with the plain lerp.  out is [Q, K, C, H*W].
+ * max_entries: the longest list (0 .. paradis_clim_quantile_max_entries() = 4096); it fixes the tile: one workgroup
+ * owns paradis_clim_quantile_cells(max_entries) adjacent cells of one (slot, channel) plane, their keys in LDS, sorted
+ * there.  A list longer than max_entries is CLAMPED to its first max_entries entries and reported through *flag, as a
+ * row, column or list bound outside the store is.  No atomics, no zero fill: bit-identical run to run.  K == 0, C == 0
+ * or Q == 0 does nothing.  rc 1 before any HIP call for a bad shape, a missing pointer, N < 0, Q > 8, a level outside
+ * [0, 1], max_entries outside its range, min_count < 1, or C * tiles above the launch limit.
+ * H*W % 4 == 0 with a 16-byte (float32) / 8-byte (packed) aligned store takes 16 B / 8 B loads, anything else scalar
+ * loads: the same bits either way.
+ * Algorithmic HBM bytes: N*C*H*W*(4 | 2) read + 4*Q*K*C*H*W written. */
+int paradis_clim_quantile_max_entries(void);
+int paradis_clim_quantile_cells(int max_entries);
+int paradis_clim_quantile(const float* store, int64_t T, int F, int H, int W, const int64_t* ptr, const int64_t* rows,
+                          int64_t N, int K, int max_entries, const int* cols, int C, const double* q_host, int Q,
+                          int min_count, float* out, int* flag, void* stream);
+int paradis_clim_quantile_packed(const uint16_t* codes, const float* params, const int* domain, int64_t T, int F, int H,
+                                 int W, const int64_t* ptr, const int64_t* rows, int64_t N, int K, int max_entries,
+                                 const int* cols, int C, const double* q_host, int Q, int min_count, float* out,
+                                 int* flag, void* stream);
+
 /* ---- Zonal power spectra of forecast and truth (ABI 10, additive), csrc/spectrum.hip: at which scales a forecast has
  * gone wrong.  The project's own definition, in the spirit of WeatherBench-2's ZonalEnergySpectrum; not pinned against it.
  * One launch pair on `stream`, no host synchronisation, no memset or copy nodes, no atomics (bit-identical run to run);

@@ -138,6 +138,10 @@ SIGNATURES = {
     "paradis_clim_mean": (I, [P, L, I, I, I, P, P, P, L, I, P, I, P, P, P]),
     "paradis_clim_mean_packed": (I, [P, P, P, L, I, I, I, P, P, P, L, I, P, I, P, P, P]),
     "paradis_spherical_winds_inplace": (I, [P, P, P, I, P, I, P, I, I, I, I, P]),
+    "paradis_clim_quantile_max_entries": (I, []),
+    "paradis_clim_quantile_cells": (I, [I]),
+    "paradis_clim_quantile": (I, [P, L, I, I, I, P, P, L, I, I, P, I, P, I, I, P, P, P]),
+    "paradis_clim_quantile_packed": (I, [P, P, P, L, I, I, I, P, P, L, I, I, P, I, P, I, I, P, P, P]),
     "paradis_spectrum_rows": (I, []),
     "paradis_spectrum_fft_max_w": (I, []),
     "paradis_spectrum_direct_max_w": (I, []),

@@ -19,7 +19,12 @@ rounding; ``w`` of a pressure level also divides by the level's temperature, so 
 Cartesian wind, mean temperature), which differs from the mean of the rows' ``w`` in second order of the temperature's
 relative variation.
 
-No CPU fallback: ``build`` needs the store on the HIP device.  ``ClimPlan`` is host-only.
+``build_quantiles`` gives, for the same lists, per-cell QUANTILES instead of the mean (``csrc/quantile.hip``; the
+definition is in its docstring): the per-cell thresholds of ``events.EventTable``, ``neighbourhood.FractionsTable`` and
+``probability.ProbabilityTable``, which take ``QuantileClimatology.field(...)`` as their ``climatology=`` and
+``quantile_event(name)`` as an event.
+
+No CPU fallback: ``build`` and ``build_quantiles`` need the store on the HIP device.  ``ClimPlan`` is host-only.
 """
 from __future__ import annotations
 
@@ -268,3 +273,194 @@ def build(store, plan: ClimPlan, spec=None, *, names: Optional[Sequence[str]] = 
     if int(flag.item()):
         raise RuntimeError("climatology.build: a list entry fell outside the store (clamped by the kernel)")
     return Climatology(data, plan, names, winds)
+
+
+# ---------------------------------------------------------------------------------- quantiles
+def max_quantile_entries() -> int:
+    """the longest slot list ``clim_quantile`` takes (``paradis_clim_quantile_max_entries()``)"""
+    return int(_lib.lib.paradis_clim_quantile_max_entries())
+
+
+def _levels(who: str, q) -> np.ndarray:
+    """1 to 8 distinct levels in [0, 1] as float64"""
+    try:
+        a = np.asarray([q] if np.isscalar(q) else list(q), np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: q must be a number or a list of numbers in [0, 1], got {q!r}") from None
+    if not 1 <= a.size <= 8:
+        raise ValueError(f"{who}: {a.size} levels, 1 to 8 go into one launch")
+    bad = ~((a >= 0.0) & (a <= 1.0))
+    if bool(bad.any()):
+        raise ValueError(f"{who}: level {a[np.flatnonzero(bad)[0]]!r} is outside [0, 1]")
+    if np.unique(a).size != a.size:
+        dup = [float(v) for v in a if int((a == v).sum()) > 1][0]
+        raise ValueError(f"{who}: level {dup!r} is given twice")
+    return np.ascontiguousarray(a)
+
+
+def clim_quantile(store, ptr: torch.Tensor, rows: torch.Tensor, cols: torch.Tensor, q, *,
+                  max_entries: Optional[int] = None, min_count: int = 1, out: Optional[torch.Tensor] = None,
+                  flag: Optional[torch.Tensor] = None):
+    """The launch over whatever the store holds: ``paradis_clim_quantile`` for a float32 store,
+    ``paradis_clim_quantile_packed`` for a packed one.  Device tables ``ptr`` int64 ``[K + 1]``, ``rows`` int64 ``[N]``,
+    ``cols`` int32 ``[C]`` as ``clim_mean`` takes them; ``q``: 1 to 8 distinct levels in [0, 1] (host).  Returns ``(out
+    [Q, K, C, H, W] float32, flag [1] int32)``.  No host synchronisation: ``max_entries``, the longest list, is the
+    caller's knowledge (``ClimPlan.entries.max()``); it fixes the tile, and without it the launch takes the tile of the
+    longest list supported (``max_quantile_entries()``, the slowest).  A list longer than ``max_entries`` is cut to its
+    first ``max_entries`` entries and raises ``flag``, as a row, column or list bound outside the store does.
+    ``build_quantiles`` is the public way in."""
+    T, F, H, W = store.shape
+    dev = store.device
+    require_hip(store.data if store.packing is None else store.plane_params, out)
+    K, C, N = int(ptr.numel()) - 1, int(cols.numel()), int(rows.numel())
+    for name, t, dtype in (("ptr", ptr, torch.int64), ("rows", rows, torch.int64), ("cols", cols, torch.int32)):
+        if t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError(f"clim_quantile: {name} must be a contiguous 1-D {dtype} tensor on {dev}")
+    if K < 0:
+        raise ValueError("clim_quantile: ptr needs K + 1 entries")
+    levels = _levels("clim_quantile", q)
+    Q = int(levels.size)
+    longest = max_quantile_entries()
+    max_entries = longest if max_entries is None else int(max_entries)
+    if not 0 <= max_entries <= longest:
+        raise ValueError(f"clim_quantile: max_entries must lie in [0, {longest}], got {max_entries}")
+    if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 1:
+        raise ValueError(f"clim_quantile: min_count must be an integer >= 1, got {min_count!r}")
+    if out is None:
+        out = torch.empty(Q, K, C, H, W, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (Q, K, C, H, W) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"clim_quantile: out must be contiguous float32 {(Q, K, C, H, W)} on {dev}")
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    tail = (T, F, H, W, dptr(ptr), dptr(rows), N, K, max_entries, dptr(cols), C, levels.ctypes.data, Q, int(min_count),
+            dptr(out), dptr(flag), stream_ptr())
+    P = H * W
+    if store.packing is None:
+        _lib.call("clim_quantile", 4.0 * N * C * P + 4.0 * Q * K * C * P, dptr(store.data), *tail)
+    else:
+        _lib.call("clim_quantile_packed", 2.0 * N * C * P + 4.0 * Q * K * C * P, dptr(store.codes),
+                  dptr(store.plane_params), dptr(store.domain_dev), *tail)
+    return out, flag
+
+
+class QuantileClimatology:
+    """What ``build_quantiles`` returns.  ``data``: ``[Q, K, C, H, W]`` float32 on the store's device, compact over the
+    chosen ``names`` (physical units; NaN where a cell kept fewer than ``min_count`` values); ``levels``: the ``Q``
+    levels as floats; ``plan``.
+
+    ``index(times_us)``: as ``Climatology.index``.  ``level(q)``: the ``[K, C, H, W]`` view of one level.
+    ``field(state_names, levels)``: a new ``[K, len(state_names), H, W]`` tensor in a state's channel layout, in which
+    channel ``name`` holds the level ``levels[name]`` (a dict name -> q) and every other plane is NaN, so that an anomaly
+    source on such a channel counts no cell - what ``EventTable``, ``FractionsTable`` and ``ProbabilityTable`` take as
+    ``climatology=`` beside ``quantile_event(name)``.  Plain indexing, no kernel.  A table holds ONE climatology, so two
+    levels of the same channel (q10 and q90 of temperature) need two fields and two tables."""
+
+    def __init__(self, data: torch.Tensor, plan: ClimPlan, names, levels, min_count: int = 1):
+        self.data, self.plan, self.names = data, plan, list(names)
+        self.levels = [float(v) for v in levels]
+        self.min_count = int(min_count)
+
+    def index(self, times_us) -> torch.Tensor:
+        return torch.from_numpy(self.plan.slot_of(times_us)).to(self.data.device)
+
+    def _level_pos(self, who: str, q) -> int:
+        try:
+            return self.levels.index(float(q))
+        except (TypeError, ValueError):
+            raise ValueError(f"QuantileClimatology.{who}: level {q!r} was not built (levels {self.levels})") from None
+
+    def level(self, q) -> torch.Tensor:
+        return self.data[self._level_pos("level", q)]
+
+    def field(self, state_names: Sequence[str], levels: dict) -> torch.Tensor:
+        state_names = [str(n) for n in state_names]
+        if not isinstance(levels, dict) or not levels:
+            raise ValueError("QuantileClimatology.field: levels must be a non-empty dict name -> q")
+        _, K, _, H, W = self.data.shape
+        out = torch.full((K, len(state_names), H, W), float("nan"), dtype=torch.float32, device=self.data.device)
+        for name, q in levels.items():
+            if name not in state_names:
+                raise ValueError(f"QuantileClimatology.field: '{name}' is not among the state's names")
+            if name not in self.names:
+                raise ValueError(f"QuantileClimatology.field: no quantiles were built for '{name}'")
+            out[:, state_names.index(name)] = self.data[self._level_pos("field", q), :, self.names.index(name)]
+        return out
+
+
+def quantile_event(name: str, direction: str = "ge") -> dict:
+    """The events-dict entry of "``name`` beyond its per-cell quantile": ``{"source": ("anomaly", name), "thresholds":
+    [0.0], "direction": direction}`` for a table whose ``climatology=`` is ``QuantileClimatology.field(...)``.  The
+    anomaly ``x - q`` of two finite fp32 values is zero only when they are equal (no flush to zero), so ``x - q >= 0``
+    decides exactly ``x >= q`` (``"le"``: ``x <= q``)."""
+    if direction not in ("ge", "le"):
+        raise ValueError(f"quantile_event: direction must be 'ge' or 'le', got {direction!r}")
+    return {"source": ("anomaly", str(name)), "thresholds": [0.0], "direction": direction}
+
+
+def build_quantiles(store, plan: ClimPlan, q, spec=None, *, names: Optional[Sequence[str]] = None,
+                    min_count: int = 1) -> QuantileClimatology:
+    """The quantile climatology of ``store`` (a ``dataset.DeviceStore`` on the HIP device, float32 or packed; never
+    written) by ``plan``, at the levels ``q`` (1 to 8 distinct numbers in [0, 1]), for the channels ``names`` (default
+    ``spec.names``), in physical units.
+
+    Definition (the project's OWN, like ``ClimPlan``'s; not pinned against any package).  For slot ``k``, channel ``c``
+    and cell ``p``: the values ``x[rows[j], col[c], p]`` over the slot's list entries ``j``, UNWEIGHTED; ``-0.0`` is read
+    as ``+0.0``; NaN and +-Inf are skipped (the rule of ``clim_mean`` and ``StoreStats``).  With ``m`` values kept,
+    ``v[0] <= ... <= v[m-1]`` ascending, and a level ``q``::
+
+        pos = q * (m - 1);  lo = floor(pos);  hi = min(lo + 1, m - 1);  frac = pos - lo
+        out = float32(v[lo] + (v[hi] - v[lo]) * frac)        in double, one rounding
+        out = NaN   when m < min_count   (min_count >= 1)
+
+    numpy's ``method="linear"`` position rule with the plain lerp (numpy changes its lerp form at ``frac >= 0.5``, which
+    moves a rare result by one float32 ulp).
+
+    One launch of ``paradis_clim_quantile`` (``csrc/quantile.hip``: keys in LDS, a bitonic sort per cell; bit-identical
+    run to run) and one read of the launch's flag word.  Refused: what ``build`` refuses (a CPU store, a plan made for
+    other times, a name the store does not hold); a plan with ``weights="gaussian"`` (quantiles are unweighted); bad
+    levels; a slot whose list is longer than ``max_quantile_entries()``; and, with a ``PostSpec`` built with
+    ``winds=True``, any name of a wind triple - the quantile of a Cartesian component is not the quantile of ``u`` or
+    ``v``: pass ``names=`` without the winds."""
+    who = "climatology.build_quantiles"
+    if spec is None and names is None:
+        raise ValueError(f"{who}: a PostSpec or names=[...] is needed")
+    names = [str(n) for n in (spec.names if names is None else names)]
+    if spec is not None:
+        for name in names:
+            if name not in spec.names:
+                raise ValueError(f"{who}: channel '{name}' is not among spec.names")
+        if spec.winds:
+            wind = {spec.names[c] for c in list(spec.ix) + list(spec.iy) + list(spec.iz) + list(spec.sfc)}
+            for name in names:
+                if name in wind:
+                    raise ValueError(f"{who}: '{name}' belongs to a wind triple of a spec built with winds=True; the "
+                                     f"quantile of a Cartesian component is not the quantile of u or v: pass names= "
+                                     f"without the winds")
+    if plan.weights != "boxcar":
+        raise ValueError(f"{who}: the plan has weights='{plan.weights}', but quantiles are unweighted: make the plan "
+                         f"with weights='boxcar'")
+    levels = _levels(who, q)
+    if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 1:
+        raise ValueError(f"{who}: min_count must be an integer >= 1, got {min_count!r}")
+    if not np.array_equal(plan.times_us, store.times_us.numpy()):
+        raise ValueError(f"{who}: the plan was made for other times than the store's times_us")
+    column = {name: j for j, name in enumerate(store.features)}
+    for name in names:
+        if name not in column:
+            raise ValueError(f"{who}: channel '{name}' is not among the store's features")
+    longest = int(plan.entries.max()) if plan.entries.size else 0
+    if longest > max_quantile_entries():
+        k = int(np.argmax(plan.entries))
+        raise ValueError(f"{who}: slot {k} (day of year {plan.days[k // len(plan.hours)]}, hour "
+                         f"{plan.hours[k % len(plan.hours)]}) has {longest} entries, at most {max_quantile_entries()} "
+                         f"can be sorted per cell: a shorter window or fewer years")
+    if torch.device(store.device).type == "cpu":
+        raise ValueError(f"{who}: the quantiles are built on the HIP device (no CPU fallback); got a CPU store")
+    dev = store.device
+    ptr, rows, _ = plan.lists()
+    ptr, rows = torch.from_numpy(ptr).to(dev), torch.from_numpy(rows).to(dev)
+    cols = torch.tensor([column[n] for n in names], dtype=torch.int32, device=dev)
+    data, flag = clim_quantile(store, ptr, rows, cols, levels, max_entries=longest, min_count=int(min_count))
+    if int(flag.item()):
+        raise RuntimeError(f"{who}: a list entry fell outside the store (clamped by the kernel)")
+    return QuantileClimatology(data, plan, names, levels, int(min_count))
