@@ -182,10 +182,12 @@ def read(acc: torch.Tensor, counts: torch.Tensor, sync_dist: bool) -> Tuple[np.n
 class LeadTable:
     """The base of the per-lead tables.  A subclass states how messages call it (``IT`` / ``IT_HAS``: "the table" /
     "the table has") and how ``Forecaster.run`` does (``NOUN``, ``HAS``, ``NEEDS``), and whether its ``update`` takes a
-    ``clim_index``; its constructor calls ``__init__``, then ``_set_grid`` and ``_set_climatology`` as far as it has
-    latitudes, bands and a climatology, in the order its checks fire."""
+    ``clim_index`` and how many batch entries share one truth (``members``: 1, or an ensemble table's own); its
+    constructor calls ``__init__``, then ``_set_grid`` and ``_set_climatology`` as far as it has latitudes, bands and a
+    climatology, in the order its checks fire."""
     IT = IT_HAS = NOUN = HAS = NEEDS = ""
     TAKES_CLIM_INDEX = True
+    members = 1
 
     def __init__(self, names: Sequence[str], n_leads: int, device):
         self.who = type(self).__name__

@@ -1,6 +1,6 @@
-// Event sources - the one definition of what events.hip (contingency tables) and fss.hip (fractions skill score) decide
-// per cell: the source kinds and limits, the host tables and their checks, the planes of a (sample, source), the value
-// of a source at a cell and its validity, the thresholds.  Include in a unit built with -ffp-contract=off.
+// Event sources - the one definition of what events.hip (contingency tables), fss.hip (fractions skill score) and
+// probability.hip (joint histogram of an ensemble) decide per cell, and the one frame around their per-cell loops.
+// Include in a unit built with -ffp-contract=off.
 //   plain    x = v[c0]
 //   speed    x = sqrtf(v[c0] * v[c0] + v[c1] * v[c1])        (mul, mul, add, sqrt: uncontracted)
 //   anomaly  x = v[c0] - clim[clim_index[b]][c0]
@@ -8,9 +8,19 @@
 // "le" is sign = -1, thr' = -thr on the host).  src_table [S][4] = {kind, c0, c1, nthr} and thr_table [S][1 + TMAX] =
 // {sign, thr'...} are HOST memory, checked here and handed to the kernel as arguments: no copy node, and a captured launch
 // keeps them.
-// Work layout of both decision kernels: a workgroup of 256 threads owns plane_rows(W) ~ PLANE_PIECE / W whole rows of one
-// (sample, source) pair - block = pair * ngroups + group -, so clim_index[b], the source's table row and every plane base
-// are workgroup-uniform.
+// Work layout of the decision kernels: a workgroup of 256 threads owns `rows` whole rows of one (sample, source) pair -
+// plane_rows(W) ~ PLANE_PIECE / W of them, or the unit's own number; block = pair * ngroups + group -, so clim_index[b],
+// the source's table row and every plane base are workgroup-uniform.
+// Once for the three units:
+//   host    event_shape_check (in front of a unit's B == 0 return), event_launch_prologue (every check behind it,
+//           event_sources_fill, the two grids), launch_lead_finish
+//   device  source_planes, source_thresholds, event_source_value / event_cell (the decision), lead_finish_kernel
+//           (acc += sum_b partial)
+// Not here, on purpose: the decision kernels themselves - the blockIdx decode, the climatology-slot test, the KIND and
+// threshold dispatch - and their per-cell loops.  The kernels sit at the scalar-register limit (SourceInputs carries 832
+// bytes of tables as kernel arguments; scalars spill to vector lanes), and written over shared helpers (a decode struct,
+// dispatch over lambdas) they compiled to other register counts and other spill placement than written out, and two
+// units measured slower.  Each unit keeps its kernel, written out.
 #pragma once
 #include "common.h"
 #include "stream_common.h"
@@ -48,11 +58,11 @@ inline int event_shape_check(const char* who, const char* kname, const float* cl
   return 0;
 }
 
-// checks the planes, the strides and the two host tables (non-null: the entry point's own check) and fills `in`;
-// vec: every plane quad is one aligned 16-byte load.  Returns the entry point's rc
+// checks the planes, the strides and the two host tables (non-null: the caller's check) and fills `in`; rows: the rows
+// of a workgroup; vec: every plane quad is one aligned 16-byte load.  Returns the entry point's rc
 inline int event_sources_fill(const char* who, SourceInputs& in, bool& vec, const float* fc, int64_t fc_bs,
                               const float* truth, int64_t truth_bs, const float* clim, const int* clim_index, int K,
-                              const int* src_table, const float* thr_table, int C, int S, int H, int W) {
+                              const int* src_table, const float* thr_table, int C, int S, int H, int W, int rows) {
   const int64_t P = (int64_t)H * W;
   PD_REQUIRE(P < (1ll << 31) - PLANE_PIECE, "%s: a plane of %d x %d cells is too large", who, H, W);
   PD_REQUIRE(fc_bs >= P * C && truth_bs >= P * C, "%s: batch strides shorter than one state", who);
@@ -78,10 +88,57 @@ inline int event_sources_fill(const char* who, SourceInputs& in, bool& vec, cons
   in.fc = fc; in.truth = truth; in.clim = clim; in.clim_index = clim_index;
   in.fc_bs = fc_bs; in.truth_bs = truth_bs; in.P = P;
   in.C = C; in.S = S; in.H = H; in.W = W; in.K = K;
-  in.rows = plane_rows(W);
+  in.rows = rows;
   in.ngroups = (int)ceil_div64(H, in.rows);         // (<= H)
   vec = (W % 4 == 0) && aligned16(fc) && aligned16(truth) && (fc_bs % 4 == 0) && (truth_bs % 4 == 0) &&
         (clim == nullptr || aligned16(clim));
+  return 0;
+}
+
+// what event_launch_prologue hands back beside the filled SourceInputs
+struct EventLaunch {
+  bool vec;
+  unsigned grid, finish_grid;   // the decision kernel's workgroups, lead_finish_kernel's blocks: both checked
+  int64_t n;                    // S H n_row, the counters of one sample's partials
+};
+
+// what differs between the units in event_launch_prologue
+struct EventUnit {
+  const char* who;
+  bool ws_ok;                 // the unit's condition on its workspace, and the tail of the message
+  const char* ws_also;
+  bool inputs_ok;             // the same for its input pointers
+  const char* inputs_which;
+  int rows;                   // rows of a decision workgroup
+  int n_row;                  // counters of a partial row
+  int row_thr = EVSRC_TMAX;   // thresholds an accumulator row holds (probability.hip: its T)
+  int64_t other_grid = 0;     // workgroups of the unit's second kernel (fss.hip: the windows)
+};
+
+// What the three entry points check behind their B == 0 return, in the order the messages fire, then the grids.  What
+// stands in front of that return differs - events_update: event_shape_check; fss_update: also W and K (and, behind the
+// return, its tables and half_y); prob_update: also M and T - and stays with each entry point, in its own order
+inline int event_launch_prologue(const EventUnit& u, SourceInputs& in, EventLaunch& L, const void* acc_lead,
+                                 const void* n_samples_lead, const float* fc, int64_t fc_bs, const float* truth,
+                                 int64_t truth_bs, const float* clim, const int* clim_index, int K,
+                                 const int* src_table, const float* thr_table, int B, int C, int S, int H, int W) {
+  const char* who = u.who;
+  PD_REQUIRE(acc_lead != nullptr && n_samples_lead != nullptr, "%s: acc_lead / n_samples_lead missing", who);
+  PD_REQUIRE(u.ws_ok, "%s: ws (workspace) missing%s", who, u.ws_also);
+  PD_REQUIRE(u.inputs_ok, "%s: null input pointer%s", who, u.inputs_which);
+  const int rc = event_sources_fill(who, in, L.vec, fc, fc_bs, truth, truth_bs, clim, clim_index, K, src_table,
+                                    thr_table, C, S, H, W, u.rows);
+  if (rc != 0) return rc;
+  for (int s = 0; s < S; ++s)
+    PD_REQUIRE(in.src[s][3] <= u.row_thr, "%s: source %d has %d thresholds, the accumulator row holds T = %d", who, s,
+               in.src[s][3], u.row_thr);
+  const int64_t groups = (int64_t)B * S * in.ngroups;
+  PD_REQUIRE(groups < (1ll << 31) && u.other_grid < (1ll << 31), "%s: %lld workgroups exceed the grid limit", who,
+             (long long)std::max(groups, u.other_grid));
+  L.n = (int64_t)S * H * u.n_row;
+  PD_REQUIRE(ceil_div64(L.n, 256) < (1ll << 31), "%s: %lld counters exceed the grid limit", who, (long long)L.n);
+  L.grid = (unsigned)groups;
+  L.finish_grid = (unsigned)ceil_div64(L.n, 256);
   return 0;
 }
 
@@ -164,3 +221,34 @@ __device__ __forceinline__ bool event_cell(bool inside, float fa, float ta, floa
   if (KIND == EVSRC_ANOMALY) ok = ok && __builtin_isfinite(cv);
   return ok;
 }
+
+namespace {
+
+// one thread per (source, row, counter of a partial row), n = S H n_row of them: acc += sum_b partial, b ascending, an
+// ordinary read-modify-write (launches of one stream are ordered); thread 0 adds B to the lead's sample count.  T:
+// unsigned or unsigned long long; an accumulator row has acc_row >= n_row entries, the partial row is its prefix
+template <class T>
+__global__ void __launch_bounds__(256) lead_finish_kernel(const T* __restrict__ partial, int64_t* __restrict__ acc,
+                                                          int64_t* __restrict__ n_samples, int B, int64_t n, int n_row,
+                                                          int acc_row) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) n_samples[0] += B;
+  if (i >= n) return;
+  int64_t s = 0;
+  for (int b = 0; b < B; ++b) s += (int64_t)partial[(int64_t)b * n + i];
+  int64_t at = i;
+  if (acc_row != n_row) {              // (uniform: events.hip and probability.hip never pay the 64-bit division)
+    const int64_t r = i / n_row;
+    at = r * acc_row + (i - r * n_row);
+  }
+  acc[at] += s;
+}
+
+template <class T>
+inline void launch_lead_finish(const EventLaunch& L, const T* partial, int64_t* acc_lead, int64_t* n_samples_lead, int B,
+                               int n_row, int acc_row, hipStream_t st) {
+  hipLaunchKernelGGL(lead_finish_kernel<T>, dim3(L.finish_grid), dim3(256), 0, st, partial, acc_lead, n_samples_lead, B,
+                     L.n, n_row, acc_row);
+}
+
+}  // namespace

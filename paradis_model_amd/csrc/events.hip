@@ -1,10 +1,13 @@
 // Event verification - one pass over a forecast state and its truth [B, C, H, W] (physical units, fp32, each with its own
 // batch stride) that counts, per sample b, event source s and latitude row h, the cells of the 2x2 contingency table of
 // "value beyond a threshold" in forecast against truth, and a finishing kernel that adds the counts to the int64 row of
-// one lead.  The sources, their host tables, validity and the event decision are event_source.h's (fss.hip decides the
-// same events through the same header): the event is sign * x >= thr'[j], a cell is valid iff every value it reads is
-// finite, and a sample whose clim_index is outside [0, K) has no valid cell for an anomaly source - nothing of
-// that slot is read.  Per valid cell, F: the forecast is beyond thr'[j], O: the truth is.  Per row, EV_CNT counters:
+// one lead.  The sources, their host tables, validity and the event decision are event_source.h's (fss.hip and
+// probability.hip decide the same events through the same header), and so are the entry point's checks behind its
+// B == 0 return (event_launch_prologue) and the finishing kernel (lead_finish_kernel).  This unit keeps its decision
+// kernel written out, its counters and its workspace.  The event is sign * x >= thr'[j],
+// a cell is valid iff every value it reads is finite, and a sample whose clim_index is outside [0, K) has no valid cell
+// for an anomaly source - nothing of that slot is read.  Per valid cell, F: the forecast is beyond thr'[j], O: the truth
+// is.  Per row, EV_CNT counters:
 //   [0] nV    [1 + j] nF[j]    [1 + TMAX + j] nO[j]    [1 + 2 TMAX + j] nFO[j]         (0 for j >= nthr)
 // Everything after the decision is integer: the result is exact and the same whichever path produced it.
 //
@@ -29,8 +32,7 @@
 
 namespace {
 
-constexpr int EV_TMAX = EVSRC_TMAX;
-constexpr int EV_CNT = 1 + 3 * EV_TMAX;           // counters per (source, row)
+constexpr int EV_CNT = 1 + 3 * EVSRC_TMAX;        // counters per (source, row)
 
 struct EventsArgs {
   SourceInputs in;
@@ -82,8 +84,8 @@ __device__ __forceinline__ void events_count_rows(const SourcePlanes& p, float s
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         mine = lane == 1 + j ? nF[j] : mine;
-        mine = lane == 1 + EV_TMAX + j ? nO[j] : mine;
-        mine = lane == 1 + 2 * EV_TMAX + j ? nFO[j] : mine;
+        mine = lane == 1 + EVSRC_TMAX + j ? nO[j] : mine;
+        mine = lane == 1 + 2 * EVSRC_TMAX + j ? nFO[j] : mine;
       }
       if (lane < EV_CNT) out[(int64_t)h * EV_CNT + lane] = mine;
       nV = 0;
@@ -99,7 +101,7 @@ __device__ __forceinline__ void events_count_rows(const SourcePlanes& p, float s
 template <int KIND, bool VEC>
 __device__ __forceinline__ void events_count_kind(const SourcePlanes& p, const float* __restrict__ tab, int nthr, int W,
                                                   int h0, int h1, unsigned* __restrict__ out) {
-  float th[EV_TMAX];
+  float th[EVSRC_TMAX];
   const float sign = source_thresholds(tab, nthr, th);
   if (nthr <= 1) {
     const float t1[1] = {th[0]};
@@ -143,22 +145,9 @@ __global__ void __launch_bounds__(256) events_kernel(EventsArgs a) {
   }
 }
 
-// one thread per (source, row, counter): acc += sum_b partial, an ordinary read-modify-write (launches of one stream
-// are ordered); thread 0 adds B to the lead's sample count
-__global__ void __launch_bounds__(256) events_finish_kernel(const unsigned* __restrict__ partial,
-                                                            int64_t* __restrict__ acc,
-                                                            int64_t* __restrict__ n_samples, int B, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) n_samples[0] += B;
-  if (i >= n) return;
-  int64_t s = 0;
-  for (int b = 0; b < B; ++b) s += (int64_t)partial[(int64_t)b * n + i];
-  acc[i] += s;
-}
-
 }  // namespace
 
-extern "C" int paradis_events_max_thresholds(void) { return EV_TMAX; }
+extern "C" int paradis_events_max_thresholds(void) { return EVSRC_TMAX; }
 
 extern "C" int paradis_events_max_sources(void) { return EVSRC_SMAX; }
 
@@ -175,26 +164,17 @@ extern "C" int paradis_events_update(const float* fc, int64_t fc_bs, const float
                                      int B, int C, int S, int H, int W, void* stream) {
   int rc = event_shape_check("events_update", "K", clim, clim_index, K, B, C, S, H, W);
   if (rc != 0 || B == 0) return rc;
-  PD_REQUIRE(acc_lead != nullptr && n_samples_lead != nullptr, "events_update: acc_lead / n_samples_lead missing");
-  PD_REQUIRE(ws != nullptr, "events_update: ws (workspace) missing");
-  PD_REQUIRE(fc && truth && src_table && thr_table, "events_update: null input pointer");
   EventsArgs a;
-  bool vec;
-  rc = event_sources_fill("events_update", a.in, vec, fc, fc_bs, truth, truth_bs, clim, clim_index, K, src_table,
-                          thr_table, C, S, H, W);
+  EventLaunch L;
+  const EventUnit u{"events_update", ws != nullptr, "", fc && truth && src_table && thr_table, "", plane_rows(W), EV_CNT};
+  rc = event_launch_prologue(u, a.in, L, acc_lead, n_samples_lead, fc, fc_bs, truth, truth_bs, clim, clim_index, K,
+                             src_table, thr_table, B, C, S, H, W);
   if (rc != 0) return rc;
-  const int64_t ngroups = a.in.ngroups, pairs = (int64_t)B * S;
-  PD_REQUIRE(pairs * ngroups < (1ll << 31), "events_update: %lld workgroups exceed the grid limit",
-             (long long)(pairs * ngroups));
-  const int64_t n = (int64_t)S * H * EV_CNT;
-  PD_REQUIRE(ceil_div64(n, 256) < (1ll << 31), "events_update: %lld counters exceed the grid limit", (long long)n);
   a.partial = static_cast<unsigned*>(ws);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(pairs * ngroups));
-  if (vec) hipLaunchKernelGGL(events_kernel<true>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(events_kernel<false>, grid, dim3(256), 0, st, a);
-  hipLaunchKernelGGL(events_finish_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, a.partial, acc_lead,
-                     n_samples_lead, B, n);
+  if (L.vec) hipLaunchKernelGGL(events_kernel<true>, dim3(L.grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(events_kernel<false>, dim3(L.grid), dim3(256), 0, st, a);
+  launch_lead_finish(L, a.partial, acc_lead, n_samples_lead, B, EV_CNT, EV_CNT, st);
   PD_CHECK_LAUNCH("events_update");
   return 0;
 }

@@ -22,7 +22,10 @@
 //      33 * 129 = 4257) and slides that sum to its next columns, squares and multiplies per threshold into 32-bit
 //      sums of its at most 6 columns (6 * 4257^2 = 1.1e8); those are summed over the 16 lanes of a DPP row in 32 bits
 //      (1.7e9 < 2^32) and from there on in 64 bits through LDS: a row's sum reaches 1440 * 4257^2 = 2.6e10.
-//   3. fss_finish_kernel: acc += sum_b partials, n_samples += B, ordinary read-modify-writes.
+//   3. lead_finish_kernel (event_source.h): acc += sum_b partials, n_samples += B, ordinary read-modify-writes; a partial
+//      row is the prefix of an acc row of FSS_CNT entries.
+// event_source.h also holds the entry point's checks behind its B == 0 return (event_launch_prologue, which checks the
+// window kernel's grid too); this unit keeps its two kernels written out.
 // No atomics, no host synchronisation, no memset or copy nodes; the inputs are only read, and only the sources' planes.
 // Workspace: the mask planes, then the partials uint64 [B][S][H][1 + 2 TMAX + 3 K TMAX], a prefix of an acc row.
 #include "common.h"
@@ -35,14 +38,13 @@
 
 namespace {
 
-constexpr int FSS_TMAX = EVSRC_TMAX;
 constexpr int FSS_KMAX = 8;                        // scales per launch
 constexpr int FSS_MAX_HY = 16;                     // latitude half-width, rows
 constexpr int FSS_MAX_HX = 64;                     // longitude half-width, cells
 constexpr int FSS_NC = 6;                          // columns per thread of the window kernel
 constexpr int FSS_MAX_W = 1440;                    // longitudes
-constexpr int FSS_HEAD = 1 + 2 * FSS_TMAX;         // nV, nF[TMAX], nO[TMAX]
-constexpr int FSS_CNT = FSS_HEAD + 3 * FSS_KMAX * FSS_TMAX;      // int64 per (source, row) of acc
+constexpr int FSS_HEAD = 1 + 2 * EVSRC_TMAX;       // nV, nF[TMAX], nO[TMAX]
+constexpr int FSS_CNT = FSS_HEAD + 3 * FSS_KMAX * EVSRC_TMAX;      // int64 per (source, row) of acc
 static_assert(FSS_MAX_W <= 256 * FSS_NC, "a thread of the window kernel owns at most FSS_NC columns");
 static_assert(2 * FSS_MAX_HY + 1 <= 255, "a vertical count fits a byte lane");
 static_assert((2 * FSS_MAX_HY + 1) * (2 * FSS_MAX_HX + 1) <= 65535, "a window count fits a 16-bit lane");
@@ -55,7 +57,7 @@ inline int fss_rows() { return 8; }
 inline size_t mask_bytes(int B, int S, int H, int W) {
   return ((size_t)B * S * H * W * sizeof(uint16_t) + 15) / 16 * 16;
 }
-inline int row_counters(int K) { return FSS_HEAD + 3 * K * FSS_TMAX; }
+inline int row_counters(int K) { return FSS_HEAD + 3 * K * EVSRC_TMAX; }
 
 // ---------------------------------------------------------------------------------------------- 1. the decision
 struct DecideArgs {
@@ -72,14 +74,14 @@ __device__ __forceinline__ void decide_rows_of_wave(const SourcePlanes& p, const
                                                     unsigned long long* __restrict__ out, int n_row) {
   const int lane = (int)(threadIdx.x & 63);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  float th[FSS_TMAX];
+  float th[EVSRC_TMAX];
   const float sign = source_thresholds(tab, nthr, th);
   const int wpr = (W + 255) / 256;                                              // walks per row
   for (int h = h0 + wave; h < h1; h += 4) {
     const int64_t row = (int64_t)h * W;
-    unsigned nV = 0, nF[FSS_TMAX], nO[FSS_TMAX];
+    unsigned nV = 0, nF[EVSRC_TMAX], nO[EVSRC_TMAX];
 #pragma unroll
-    for (int j = 0; j < FSS_TMAX; ++j) nF[j] = nO[j] = 0;
+    for (int j = 0; j < EVSRC_TMAX; ++j) nF[j] = nO[j] = 0;
 #pragma clang loop vectorize(disable) interleave(disable)
     for (int wk = 0; wk < wpr; ++wk) {
       // (source_load_walk's loads spelt out into local arrays: with the quads in a SourceQuads this loop's schedule came
@@ -104,7 +106,7 @@ __device__ __forceinline__ void decide_rows_of_wave(const SourcePlanes& p, const
         nV += count_lanes(ok);
         unsigned bits = 0;
 #pragma unroll
-        for (int j = 0; j < FSS_TMAX; ++j) {
+        for (int j = 0; j < EVSRC_TMAX; ++j) {
           const bool F = ok && sf >= th[j], O = ok && st >= th[j];
           nF[j] += count_lanes(F);
           nO[j] += count_lanes(O);
@@ -122,9 +124,9 @@ __device__ __forceinline__ void decide_rows_of_wave(const SourcePlanes& p, const
     }
     unsigned mine = lane == 0 ? nV : 0u;
 #pragma unroll
-    for (int j = 0; j < FSS_TMAX; ++j) {
+    for (int j = 0; j < EVSRC_TMAX; ++j) {
       mine = lane == 1 + j ? nF[j] : mine;
-      mine = lane == 1 + FSS_TMAX + j ? nO[j] : mine;
+      mine = lane == 1 + EVSRC_TMAX + j ? nO[j] : mine;
     }
     if (lane < FSS_HEAD) out[(int64_t)h * n_row + lane] = mine;
   }
@@ -200,7 +202,7 @@ __global__ void __launch_bounds__(256) fss_window_kernel(WindowArgs a) {
   const int h0 = g * a.rows, h1 = min(H, h0 + a.rows);
   const int ncw = (W + 255) / 256;               // columns of a thread's segment in the window sums (<= NC)
   const uint16_t* __restrict__ m = a.mask + pair * (int64_t)H * W;
-  unsigned long long* out = a.partial + pair * (int64_t)H * a.n_row + FSS_HEAD + 3 * FSS_TMAX * k;
+  unsigned long long* out = a.partial + pair * (int64_t)H * a.n_row + FSS_HEAD + 3 * EVSRC_TMAX * k;
 
   unsigned V[NC][NV];
 #pragma unroll
@@ -296,7 +298,7 @@ __global__ void __launch_bounds__(256) fss_window_kernel(WindowArgs a) {
       }
     }
     __syncthreads();
-    if (t < 3 * FSS_TMAX) {                       // entry 3 j + q of this scale: FF, OO, FO of threshold j
+    if (t < 3 * EVSRC_TMAX) {                       // entry 3 j + q of this scale: FF, OO, FO of threshold j
       unsigned long long s = 0ull;
       if (t < 3 * NT) {
 #pragma unroll
@@ -305,20 +307,6 @@ __global__ void __launch_bounds__(256) fss_window_kernel(WindowArgs a) {
       out[(int64_t)h * a.n_row + t] = s;
     }
   }
-}
-
-// ---------------------------------------------------------------------------------------------- 3. the finish
-// one thread per (source, row, counter of the partials' row): acc += sum_b partial; thread 0 adds B to the sample count
-__global__ void __launch_bounds__(256) fss_finish_kernel(const unsigned long long* __restrict__ partial,
-                                                         int64_t* __restrict__ acc, int64_t* __restrict__ n_samples,
-                                                         int B, int64_t n, int n_row) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) n_samples[0] += B;
-  if (i >= n) return;
-  int64_t s = 0;
-  for (int b = 0; b < B; ++b) s += (int64_t)partial[(int64_t)b * n + i];
-  const int64_t r = i / n_row;
-  acc[r * FSS_CNT + (i - r * n_row)] += s;
 }
 
 }  // namespace
@@ -358,23 +346,17 @@ extern "C" int paradis_fss_update(const float* fc, int64_t fc_bs, const float* t
                FSS_MAX_HY);
     ny_max = std::max(ny_max, wa.hy[k]);
   }
-  PD_REQUIRE(acc_lead != nullptr && n_samples_lead != nullptr, "fss_update: acc_lead / n_samples_lead missing");
-  PD_REQUIRE(ws != nullptr && aligned16(ws), "fss_update: ws (workspace) missing or not 16-byte aligned");
-  PD_REQUIRE(fc && truth && half_x, "fss_update: null input pointer (fc, truth, half_x)");
+  const int R = fss_rows(), n_row = row_counters(K);
+  const int64_t wgroups = ceil_div64(H, R), wgrid_n = (int64_t)B * S * K * wgroups;
   DecideArgs a;
-  bool vec;
-  rc = event_sources_fill("fss_update", a.in, vec, fc, fc_bs, truth, truth_bs, clim, clim_index, K_clim, src_table,
-                          thr_table, C, S, H, W);
+  EventLaunch L;
+  const EventUnit u{"fss_update", ws != nullptr && aligned16(ws), " or not 16-byte aligned", fc && truth && half_x,
+                    " (fc, truth, half_x)", plane_rows(W), n_row, EVSRC_TMAX, wgrid_n};
+  rc = event_launch_prologue(u, a.in, L, acc_lead, n_samples_lead, fc, fc_bs, truth, truth_bs, clim, clim_index, K_clim,
+                             src_table, thr_table, B, C, S, H, W);
   if (rc != 0) return rc;
   int nthr_max = 0;
   for (int s = 0; s < S; ++s) nthr_max = std::max(nthr_max, a.in.src[s][3]);
-  const int R = fss_rows();
-  const int64_t pairs = (int64_t)B * S, dgroups = a.in.ngroups, wgroups = ceil_div64(H, R);
-  PD_REQUIRE(pairs * dgroups < (1ll << 31) && pairs * K * wgroups < (1ll << 31),
-             "fss_update: %lld workgroups exceed the grid limit", (long long)std::max(pairs * dgroups, pairs * K * wgroups));
-  const int n_row = row_counters(K);
-  const int64_t n = (int64_t)S * H * n_row;
-  PD_REQUIRE(ceil_div64(n, 256) < (1ll << 31), "fss_update: %lld counters exceed the grid limit", (long long)n);
   a.mask = static_cast<uint16_t*>(ws);
   a.partial = reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + mask_bytes(B, S, H, W));
   a.n_row = n_row;
@@ -382,16 +364,15 @@ extern "C" int paradis_fss_update(const float* fc, int64_t fc_bs, const float* t
   wa.H = H; wa.W = W; wa.K = K; wa.rows = R; wa.ngroups = (int)wgroups; wa.n_row = n_row;
   wa.nx_cap = std::min(FSS_MAX_HX, (W - 1) / 2);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 dgrid((unsigned)(pairs * dgroups)), wgrid((unsigned)(pairs * K * wgroups));
-  if (vec) hipLaunchKernelGGL(fss_decide_kernel<true>, dgrid, dim3(256), 0, st, a);
+  const dim3 dgrid(L.grid), wgrid((unsigned)wgrid_n);
+  if (L.vec) hipLaunchKernelGGL(fss_decide_kernel<true>, dgrid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(fss_decide_kernel<false>, dgrid, dim3(256), 0, st, a);
   const bool narrow = W <= 256, few = nthr_max <= 4;
   if (narrow && few) hipLaunchKernelGGL((fss_window_kernel<1, 1>), wgrid, dim3(256), 0, st, wa);
   else if (narrow) hipLaunchKernelGGL((fss_window_kernel<1, 2>), wgrid, dim3(256), 0, st, wa);
   else if (few) hipLaunchKernelGGL((fss_window_kernel<FSS_NC, 1>), wgrid, dim3(256), 0, st, wa);
   else hipLaunchKernelGGL((fss_window_kernel<FSS_NC, 2>), wgrid, dim3(256), 0, st, wa);
-  hipLaunchKernelGGL(fss_finish_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, a.partial, acc_lead,
-                     n_samples_lead, B, n, n_row);
+  launch_lead_finish(L, a.partial, acc_lead, n_samples_lead, B, n_row, FSS_CNT, st);
   PD_CHECK_LAUNCH("fss_update");
   return 0;
 }

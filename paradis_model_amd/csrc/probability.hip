@@ -3,7 +3,9 @@
 // counts, per ensemble g, event source s, latitude row h and threshold j, the valid cells by (o, k) - o: the truth has
 // the event, k: the number of members that have it, 0 .. M - and a finishing kernel that folds the ensembles, in g
 // order, into the int64 row of one lead.  The sources, their host tables, validity and the event decision are
-// event_source.h's (events.hip and fss.hip decide the same events through the same header): the event is
+// event_source.h's (events.hip and fss.hip decide the same events through the same header), and so are the entry
+// point's checks behind its G == 0 return (event_launch_prologue, which hands prob_rows(W) to event_sources_fill) and
+// the finishing kernel (lead_finish_kernel); this unit keeps its decision kernel written out.  The event is
 // sign * x >= thr'[j]; a cell is valid iff every value it reads is finite - the truth's, the climatology cell of an
 // anomaly, all M members' -; an ensemble whose clim_index is outside [0, K) has no valid cell for an anomaly source and
 // nothing of that slot is read.  Per row, NC = 1 + 2 T (M + 1) counters (T: the table's longest threshold list):
@@ -221,19 +223,6 @@ __global__ void __launch_bounds__(256) prob_kernel(ProbArgs a) {
   }
 }
 
-// one thread per (source, row, counter): acc += sum_g partial, g ascending, an ordinary read-modify-write (launches of
-// one stream are ordered); thread 0 adds G to the lead's ensemble count
-__global__ void __launch_bounds__(256) prob_finish_kernel(const unsigned* __restrict__ partial,
-                                                          int64_t* __restrict__ acc, int64_t* __restrict__ n_samples,
-                                                          int G, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i == 0) n_samples[0] += G;
-  if (i >= n) return;
-  int64_t s = 0;
-  for (int g = 0; g < G; ++g) s += (int64_t)partial[(int64_t)g * n + i];
-  acc[i] += s;
-}
-
 inline bool prob_members_ok(int M) { return M >= 2 && M <= PR_MMAX; }
 inline bool prob_thresholds_ok(int T) { return T >= 1 && T <= EVSRC_TMAX; }
 
@@ -261,32 +250,18 @@ extern "C" int paradis_prob_update(const float* fc, int64_t fc_bs, const float* 
   PD_REQUIRE(prob_members_ok(M), "prob_update: %d members, outside [2, %d]", M, PR_MMAX);
   PD_REQUIRE(prob_thresholds_ok(T), "prob_update: T = %d thresholds per source, outside [1, %d]", T, EVSRC_TMAX);
   if (G == 0) return 0;
-  PD_REQUIRE(acc_lead != nullptr && n_samples_lead != nullptr, "prob_update: acc_lead / n_samples_lead missing");
-  PD_REQUIRE(ws != nullptr, "prob_update: ws (workspace) missing");
-  PD_REQUIRE(fc && truth && src_table && thr_table, "prob_update: null input pointer");
   ProbArgs a;
-  bool vec;
-  rc = event_sources_fill("prob_update", a.in, vec, fc, fc_bs, truth, truth_bs, clim, clim_index, K, src_table,
-                          thr_table, C, S, H, W);
-  if (rc != 0) return rc;
-  a.in.rows = prob_rows(W);                           // (event_sources_fill set the rows of events.hip's layout)
-  a.in.ngroups = (int)ceil_div64(H, a.in.rows);
-  for (int s = 0; s < S; ++s)
-    PD_REQUIRE(a.in.src[s][3] <= T, "prob_update: source %d has %d thresholds, the accumulator row holds T = %d", s,
-               a.in.src[s][3], T);
-  const int64_t ngroups = a.in.ngroups, pairs = (int64_t)G * S;
-  PD_REQUIRE(pairs * ngroups < (1ll << 31), "prob_update: %lld workgroups exceed the grid limit",
-             (long long)(pairs * ngroups));
+  EventLaunch L;
   a.M = M; a.T = T; a.NC = prob_counters(M, T);
-  const int64_t n = (int64_t)S * H * a.NC;
-  PD_REQUIRE(ceil_div64(n, 256) < (1ll << 31), "prob_update: %lld counters exceed the grid limit", (long long)n);
+  const EventUnit u{"prob_update", ws != nullptr, "", fc && truth && src_table && thr_table, "", prob_rows(W), a.NC, T};
+  rc = event_launch_prologue(u, a.in, L, acc_lead, n_samples_lead, fc, fc_bs, truth, truth_bs, clim, clim_index, K,
+                             src_table, thr_table, G, C, S, H, W);
+  if (rc != 0) return rc;
   a.partial = static_cast<unsigned*>(ws);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(pairs * ngroups));
-  if (vec) hipLaunchKernelGGL(prob_kernel<true>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(prob_kernel<false>, grid, dim3(256), 0, st, a);
-  hipLaunchKernelGGL(prob_finish_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, a.partial, acc_lead,
-                     n_samples_lead, G, n);
+  if (L.vec) hipLaunchKernelGGL(prob_kernel<true>, dim3(L.grid), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(prob_kernel<false>, dim3(L.grid), dim3(256), 0, st, a);
+  launch_lead_finish(L, a.partial, acc_lead, n_samples_lead, G, a.NC, a.NC, st);
   PD_CHECK_LAUNCH("prob_update");
   return 0;
 }

@@ -51,7 +51,7 @@ import torch
 
 from . import _lib
 from ._lib import dptr, require_hip, stream_ptr
-from ._leadtable import LeadTable, positive_int, read
+from ._leadtable import LeadTable, positive_int, read, resolve_clim_index
 from ._tables import batch_stride, workspace
 
 KINDS = {"plain": 0, "speed": 1, "anomaly": 2}
@@ -165,11 +165,12 @@ def parse_events(who: str, events, names: Sequence[str], with_climatology: bool)
 
 class EventLeadTable(LeadTable):
     """What ``EventTable`` and ``neighbourhood.FractionsTable`` share: construction up to ``parse_events``, the int64
-    accumulator rows that begin ``{nV, nF[TMAX], nO[TMAX]}`` and ``n_samples``, and the parts of ``counts`` / ``result``
-    that read them.  ``n_lon``: the number of longitudes where the constructor knows it; ``row``: the int64 entries of
-    one accumulator row, given ``tmax``.  ``probability.ProbabilityTable`` sits on it too, with rows of its own
-    (``{nV, joint[T][2][M + 1]}``): it takes the construction, ``reset``, ``_dead`` and ``_finish`` and leaves
-    ``_counts_head`` / ``_past`` alone."""
+    accumulator rows that begin ``{nV, nF[TMAX], nO[TMAX]}`` and ``n_samples``, the parts of ``counts`` / ``result``
+    that read them, ``bind`` and the one path of ``update`` into an entry point (``_launch``).  ``n_lon``: the number of
+    longitudes where the constructor knows it; ``row``: the int64 entries of one accumulator row, given ``tmax``.
+    ``probability.ProbabilityTable`` sits on it too, with rows of its own (``{nV, joint[T][2][M + 1]}``): it takes the
+    construction, ``reset``, ``bind``, ``_launch``, ``_dead`` and ``_finish`` and leaves ``_counts_head`` / ``_past``
+    alone."""
     IT = "the table"
     IT_HAS = "the table has"
 
@@ -189,6 +190,43 @@ class EventLeadTable(LeadTable):
     def reset(self) -> None:
         self.acc.zero_()
         self.n_samples.zero_()
+
+    def bind(self, W: int) -> None:
+        """states the number of longitudes ahead of the first ``update`` (which otherwise does it); ``valid_fraction``
+        needs it"""
+        W = positive_int(f"{self.who}.bind", "W", W)
+        if self.W is not None and W != self.W:
+            raise ValueError(f"{self.who}.bind: the table is bound to {self.W} longitudes already")
+        self.W = W
+
+    def _check_longitudes(self, W: int) -> None:
+        if self.W is not None and W != self.W:
+            raise ValueError(f"{self.who}.update: forecast has {W} longitudes, the table is bound to {self.W}")
+
+    def _entry_tables(self, device) -> tuple:
+        """the tables an entry point takes behind ``thr_table`` (``FractionsTable``: its half-widths)"""
+        return ()
+
+    def _launch(self, entry: str, ws_bytes: int, lead, forecast, truth, clim_index, n: int, *tail) -> None:
+        """what ``update`` does once its table has checked the arguments: ``entry`` on the current stream for ``n``
+        samples (ensembles), with the arguments every event entry point begins with, then the shape ``tail``;
+        ``ws_bytes``: what the entry point's ``*_ws_bytes`` asks for"""
+        require_hip(forecast, truth)
+        if not self.acc.is_cuda:
+            raise RuntimeError(f"{self.who}.update: the table was made with a CPU device (there is no CPU fallback)")
+        if n == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
+            return
+        C, H, W = forecast.shape[1:]
+        if self.W is None:
+            self.bind(W)
+        clim = self.climatology
+        clim_index = resolve_clim_index(self.who, self._slot0, clim, clim_index, n, forecast.device)
+        tables = self._entry_tables(forecast.device)          # (in front of the workspace, as FractionsTable had it)
+        ws = workspace(self._ws, forecast.device, int(ws_bytes))
+        _lib.call(entry, self._bytes_per_cell * n * H * W, dptr(forecast), batch_stride(forecast, C * H * W),
+                  dptr(truth), batch_stride(truth, C * H * W), dptr(clim), dptr(clim_index),
+                  0 if clim_index is None else clim.shape[0], self._src.ctypes.data, self._thr.ctypes.data, *tables,
+                  dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]), dptr(ws), *tail, stream_ptr())
 
     def _counts_head(self, sync_dist: bool):
         """one device read: ``(a, n_samples, out)`` - the accumulator, the sample counts and ``out`` with ``valid``,
@@ -279,37 +317,12 @@ class EventTable(EventLeadTable):
         super().__init__(names, lat_deg, n_leads, events, bands, weights, climatology, device,
                          row=lambda tmax: 1 + 3 * tmax)
 
-    def bind(self, W: int) -> None:
-        """states the number of longitudes ahead of the first ``update`` (which otherwise does it); ``valid_fraction``
-        needs it"""
-        if isinstance(W, bool) or int(W) != W or int(W) < 1:
-            raise ValueError(f"EventTable.bind: W must be an integer >= 1, got {W!r}")
-        if self.W is not None and int(W) != self.W:
-            raise ValueError(f"EventTable.bind: the table is bound to {self.W} longitudes already")
-        self.W = int(W)
-
-    def _check_longitudes(self, W: int) -> None:
-        if self.W is not None and W != self.W:
-            raise ValueError(f"EventTable.update: forecast has {W} longitudes, the table is bound to {self.W}")
-
     def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
                clim_index: Optional[torch.Tensor] = None) -> None:
         B, C, H, W = self._check(lead, forecast, truth, clim_index)
-        require_hip(forecast, truth)
-        if not self.acc.is_cuda:
-            raise RuntimeError("EventTable.update: the table was made with a CPU device (there is no CPU fallback)")
-        if B == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
-            return
-        if self.W is None:
-            self.bind(W)
-        clim = self.climatology
-        clim_index, K = self._clim_args(clim_index, forecast)
-        P, S = H * W, len(self.labels)
-        ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_events_ws_bytes(B, S, H, W)))
-        _lib.call("events_update", self._bytes_per_cell * B * P, dptr(forecast), batch_stride(forecast, C * P),
-                  dptr(truth), batch_stride(truth, C * P), dptr(clim), dptr(clim_index), K, self._src.ctypes.data,
-                  self._thr.ctypes.data, dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]), dptr(ws), B, C, S,
-                  H, W, stream_ptr())
+        S = len(self.labels)
+        self._launch("events_update", _lib.lib.paradis_events_ws_bytes(B, S, H, W), lead, forecast, truth, clim_index, B,
+                     B, C, S, H, W)
 
     def counts(self, sync_dist: bool = False) -> dict:
         a, n, out = self._counts_head(sync_dist)

@@ -209,9 +209,19 @@ def chunk_plan(forecast_steps: int, output_frequency: int, write_every_n: Option
 
 # ---------------------------------------------------------------------------------- the predict loop
 def _passed(scorecard, spectra, events, fractions, ensemble=None, probability=None) -> list:
-    """the verification tables given to ``run`` (``_leadtable.LeadTable``: each brings its phrases and whether its
-    ``update`` takes ``clim_index``), in the order of their refusals and of their launches"""
+    """the verification tables given to ``run`` (``_leadtable.LeadTable``: each brings its phrases, its ``members`` and
+    whether its ``update`` takes ``clim_index``), in the order of their refusals and of their launches"""
     return [t for t in (scorecard, spectra, events, fractions, ensemble, probability) if t is not None]
+
+
+def table_inputs(table, state, truth, clim_col) -> tuple:
+    """what ``table.update`` gets behind the lead for one stored state: the finished ``state`` ``[B, C, H, W]``, the truth
+    ``[B, C, H, W]`` of every ``table.members``-th batch entry - each ensemble's FIRST member: the members of one ensemble
+    share their truth and their valid time - and, where the table takes one and the run has one, the same entries of the
+    ``clim_index`` column ``[B]``.  Views only; pure."""
+    m = table.members                                    # (1: ``x[::1]`` is ``x``'s address, shape and strides)
+    clim = (clim_col[::m],) if table.TAKES_CLIM_INDEX and clim_col is not None else ()
+    return (state, truth[::m]) + clim
 
 
 class Forecaster:
@@ -234,35 +244,22 @@ class Forecaster:
     validation batch's ``true_data``) and goes through the same ``postprocess`` into a scratch state first.  A scorecard
     without ``truth``, or a truth of another ``n_stored``, is refused before the rollout starts.
 
-    ``run(..., spectra=<spectrum.Spectra>, truth=..., truth_normalized=False)``: beside or without a scorecard, the same
-    finished state and the same truth state (one ``postprocess`` of a model-space truth serves both) go through
-    ``spectra.update`` at lead ``k`` (one more launch pair on the main stream, in front of the same event).  The
-    refusals are the scorecard's: no ``truth``, a truth of another shape, fewer leads than stored states, names that are
-    not ``PostSpec.names`` (``spectra.all_names``; its ``channels=`` subset is its own business).
-
-    ``run(..., events=<events.EventTable>, truth=..., truth_normalized=False, clim_index=...)``: beside or without a
-    scorecard and spectra, the same finished state, the same truth state and the same ``clim_index`` column go through
-    ``events.update`` at lead ``k`` (one more launch pair on the main stream, right after the others and in front of
-    the same event).  The refusals are the scorecard's.
-
-    ``run(..., fractions=<neighbourhood.FractionsTable>, truth=..., truth_normalized=False, clim_index=...)``: beside or
-    without the others, the same finished state, truth state and ``clim_index`` column go through ``fractions.update``
-    at lead ``k`` (three more launches on the main stream, right after the others and in front of the same event).
-    The refusals are the event table's.
-
-    ``run(..., ensemble=<ensemble.EnsembleCard>, truth=..., truth_normalized=False)``: beside or without the others, a
-    batch of ``B = G * members`` states is scored as ``G`` ensembles, member-minor (member ``i`` of ensemble ``g`` is
-    batch entry ``g * members + i``).  ``truth`` keeps its shape ``[B, n_stored, C, H, W]``; the card is updated with
-    the finished state and ``t[::members]``, the truth of each ensemble's FIRST member: the members of one ensemble
-    share their truth, the other members' truth entries are not read by the card.  The card launches last (one more
-    launch pair on the main stream, after ``fractions`` and in front of the same event).  The refusals are the
-    scorecard's, and a ``B`` that is no multiple of ``members``.
-
-    ``run(..., probability=<probability.ProbabilityTable>, truth=..., truth_normalized=False, clim_index=...)``: beside
-    or without the others, the same member-minor batch as for ``ensemble`` goes through ``probability.update`` at lead
-    ``k`` with ``t[::members]`` and ``clim_index[::members, k]`` - the truth and the climatology slot of each ensemble's
-    FIRST member.  The table launches after ``ensemble`` (one more launch pair on the main stream, in front of the same
-    event).  The refusals are the ensemble card's.
+    Five more tables go beside or without a scorecard, each under its own keyword, any subset of the six in one run.
+    The rule is one (``table_inputs``): the same finished state and the same truth state (one ``postprocess`` of a
+    model-space truth serves all) go through each ``table.update`` at lead ``k``, with the ``clim_index`` column where
+    the table takes one, on the main stream in the order below, in front of the same event.  An ensemble table
+    (``members`` > 1) scores the batch of ``B = G * members`` states as ``G`` ensembles, member-minor (member ``i`` of
+    ensemble ``g`` is batch entry ``g * members + i``): ``truth`` and ``clim_index`` keep their shapes, the table gets
+    ``t[::members]`` and ``clim_index[::members, k]`` - the truth and the climatology slot of each ensemble's FIRST
+    member; the members share their truth and valid time, the other members' entries are not read.  The refusals are
+    the scorecard's for every table - no ``truth``, a truth of another shape, fewer leads than stored states, names
+    that are not ``PostSpec.names`` (``all_names``; a ``channels=`` subset is the table's own business) - and, for an
+    ensemble table, a ``B`` that is no multiple of its ``members``.
+        ``spectra=<spectrum.Spectra>``                        one launch pair; takes no ``clim_index``
+        ``events=<events.EventTable>``                        one launch pair
+        ``fractions=<neighbourhood.FractionsTable>``          three launches
+        ``ensemble=<ensemble.EnsembleCard>``                  one launch pair; ``members``; takes no ``clim_index``
+        ``probability=<probability.ProbabilityTable>``        one launch pair; ``members``
 
     ``run(..., encoder=<encode.EncodeSpec>, init=<(state [B, 1, C, H, W], dew [B, 1, L, H, W] or None) or None>)``: a
     flushed chunk is regrouped into the writer's named variables and BitRounded on the device (``encode.encode_chunk``,
@@ -317,12 +314,10 @@ class Forecaster:
                 raise ValueError(f"Forecaster.run: {t.HAS} {t.n_leads} leads, the rollout stores {n_stored}")
             if list(t.all_names) != list(self.spec.names):
                 raise ValueError(f"Forecaster.run: {t.NOUN}'s names are not the chunk's channel names (PostSpec.names)")
-        if ensemble is not None and B % ensemble.members != 0:
-            raise ValueError(f"Forecaster.run: the ensemble card has {ensemble.members} members, a batch of {B} states "
-                             f"is not whole ensembles")
-        if probability is not None and B % probability.members != 0:
-            raise ValueError(f"Forecaster.run: the probability table has {probability.members} members, a batch of {B} "
-                             f"states is not whole ensembles")
+        for t in tables:
+            if t.members > 1 and B % t.members != 0:
+                raise ValueError(f"Forecaster.run: {t.HAS} {t.members} members, a batch of {B} states is not whole "
+                                 f"ensembles")
         if clim_index is not None and (clim_index.dtype != torch.int32 or tuple(clim_index.shape) != (B, n_stored)):
             raise ValueError(f"Forecaster.run: clim_index must be int32 {(B, n_stored)}, got {clim_index.dtype} "
                              f"{tuple(clim_index.shape)}")
@@ -413,13 +408,7 @@ class Forecaster:
                         t = truth_phys[:, 0]
                     k = None if clim_index is None else clim_index[:, i_stored]
                     for table in tables:         # (scorecard, .., fractions, ensemble, probability: the launch order)
-                        if table is ensemble:              # one truth per ensemble: its first member's
-                            table.update(i_stored, d[:, p.slot], t[::ensemble.members])
-                        elif table is probability:         # and one climatology slot: the members share their valid time
-                            m = probability.members
-                            table.update(i_stored, d[:, p.slot], t[::m], *(() if k is None else (k[::m],)))
-                        else:
-                            table.update(i_stored, d[:, p.slot], t, *((k,) if table.TAKES_CLIM_INDEX else ()))
+                        table.update(i_stored, *table_inputs(table, d[:, p.slot], t, k))
                 i_stored += 1
             if p.flush is not None:
                 start, n = p.flush

@@ -52,8 +52,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import dptr, require_hip, stream_ptr
-from ._tables import batch_stride, workspace
+from ._lib import dptr
 from .events import EventLeadTable, _ratio, lookup, parse_events          # noqa: F401  (parse_events: importable from here)
 
 WHO = "FractionsTable"
@@ -176,28 +175,21 @@ class FractionsTable(EventLeadTable):
     def _check(self, lead, forecast, truth, clim_index):
         return super()._check(lead, forecast, truth, clim_index, n_lon=self.W)
 
+    def _entry_tables(self, device) -> tuple:
+        """``half_y`` on the host and ``half_x`` on ``device``, copied there at its first use"""
+        dev = str(device)
+        if dev not in self._half_x_dev:
+            with torch.inference_mode(False):
+                self._half_x_dev[dev] = torch.from_numpy(self.half_x).to(device)
+        return self._half_y.ctypes.data, dptr(self._half_x_dev[dev])
+
     def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
                clim_index: Optional[torch.Tensor] = None) -> None:
         B, C, H, W = self._check(lead, forecast, truth, clim_index)
-        require_hip(forecast, truth)
-        if not self.acc.is_cuda:
-            raise RuntimeError(f"{WHO}.update: the table was made with a CPU device (there is no CPU fallback)")
-        if B == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
-            return
-        clim = self.climatology
-        clim_index, K_clim = self._clim_args(clim_index, forecast)
-        dev = str(forecast.device)
-        if dev not in self._half_x_dev:
-            with torch.inference_mode(False):
-                self._half_x_dev[dev] = torch.from_numpy(self.half_x).to(forecast.device)
-        P, S, K = H * W, len(self.labels), len(self.scales)
-        ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_fss_ws_bytes(B, S, H, W, K)))
+        S, K = len(self.labels), len(self.scales)
         try:
-            _lib.call("fss_update", self._bytes_per_cell * B * P, dptr(forecast), batch_stride(forecast, C * P),
-                      dptr(truth), batch_stride(truth, C * P), dptr(clim), dptr(clim_index), K_clim,
-                      self._src.ctypes.data, self._thr.ctypes.data, self._half_y.ctypes.data,
-                      dptr(self._half_x_dev[dev]), dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]),
-                      dptr(ws), B, C, S, H, W, K, stream_ptr())
+            self._launch("fss_update", _lib.lib.paradis_fss_ws_bytes(B, S, H, W, K), lead, forecast, truth, clim_index, B,
+                         B, C, S, H, W, K)
         except RuntimeError as e:
             if "(code 1)" in str(e):               # an argument the entry point refused, before any HIP call
                 raise ValueError(f"{WHO}.update: {_lib.last_error()}") from None

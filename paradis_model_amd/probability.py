@@ -60,9 +60,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import dptr, require_hip, stream_ptr
-from ._leadtable import check_clim_index, check_member_states, positive_int, read, resolve_clim_index
-from ._tables import batch_stride, dense_state, workspace
+from ._leadtable import check_clim_index, check_member_states, read
+from ._tables import dense_state
 from .events import EventLeadTable, _ratio, lookup
 
 SCORES = ("brier", "brier_fair", "base_rate", "uncertainty", "reliability", "resolution", "bss", "roc_area")
@@ -152,20 +151,11 @@ class ProbabilityTable(EventLeadTable):
                          row=lambda tmax: 1 + self.T * 2 * (self.members + 1))      # (parse_events has set T by then)
         self._bytes_per_cell = float(sum(bytes_per_cell(k, self.members) for k in self.kinds))
 
-    def bind(self, W: int) -> None:
-        """states the number of longitudes ahead of the first ``update`` (which otherwise does it); ``valid_fraction``
-        needs it"""
-        W = positive_int(f"{self.who}.bind", "W", W)
-        if self.W is not None and W != self.W:
-            raise ValueError(f"{self.who}.bind: the table is bound to {self.W} longitudes already")
-        self.W = W
-
     def _check(self, lead, forecast, truth, clim_index=None, n_lon=None):
         """argument checks of ``update``; returns (G, C, H, W)"""
         G, W = check_member_states(self.who, self.IT_HAS, self.n_leads, self.C, self.H, self.members, lead, forecast,
                                    truth)
-        if self.W is not None and W != self.W:
-            raise ValueError(f"{self.who}.update: forecast has {W} longitudes, the table is bound to {self.W}")
+        self._check_longitudes(W)
         dense_state(forecast, "forecast", f"{self.who}.update")
         dense_state(truth, "truth", f"{self.who}.update")
         check_clim_index(self.who, self.IT_HAS, self.climatology, clim_index, G, W)
@@ -174,22 +164,9 @@ class ProbabilityTable(EventLeadTable):
     def update(self, lead: int, forecast: torch.Tensor, truth: torch.Tensor,
                clim_index: Optional[torch.Tensor] = None) -> None:
         G, C, H, W = self._check(lead, forecast, truth, clim_index)
-        require_hip(forecast, truth)
-        if not self.acc.is_cuda:
-            raise RuntimeError(f"{self.who}.update: the table was made with a CPU device (there is no CPU fallback)")
-        if G == 0:             # (empty tensors have no address to hand over; the entry point would do nothing either)
-            return
-        if self.W is None:
-            self.bind(W)
-        clim = self.climatology
-        clim_index = resolve_clim_index(self.who, self._slot0, clim, clim_index, G, forecast.device)
-        K = 0 if clim_index is None else clim.shape[0]
-        M, T, P, S = self.members, self.T, H * W, len(self.labels)
-        ws = workspace(self._ws, forecast.device, int(_lib.lib.paradis_prob_ws_bytes(G, S, H, W, M, T)))
-        _lib.call("prob_update", self._bytes_per_cell * G * P, dptr(forecast), batch_stride(forecast, C * P),
-                  dptr(truth), batch_stride(truth, C * P), dptr(clim), dptr(clim_index), K, self._src.ctypes.data,
-                  self._thr.ctypes.data, dptr(self.acc[int(lead)]), dptr(self.n_samples[int(lead):]), dptr(ws), G, M, T,
-                  C, S, H, W, stream_ptr())
+        M, T, S = self.members, self.T, len(self.labels)
+        self._launch("prob_update", _lib.lib.paradis_prob_ws_bytes(G, S, H, W, M, T), lead, forecast, truth, clim_index, G,
+                     G, M, T, C, S, H, W)
 
     def _joint(self, sync_dist: bool):
         """one device read: ``(nV [L, S, H], joint [L, S, H, T, 2, M + 1], n_samples)``"""

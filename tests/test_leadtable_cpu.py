@@ -284,3 +284,46 @@ def test_forecaster_refuses_in_the_order_scorecard_spectra_events_fractions():
                    **tables)
         assert str(e.value) == RUN_MESSAGES[(who, "needs truth")]
         del tables[RUN_KEYS[who]]
+
+
+def _member_tables(M):
+    from paradis_model_amd.ensemble import EnsembleCard
+    from paradis_model_amd.probability import ProbabilityTable
+    return {"EnsembleCard": EnsembleCard(NAMES, LAT, 2, M, device="cpu"),
+            "ProbabilityTable": ProbabilityTable(NAMES, LAT, 2, EV, M, device="cpu")}
+
+
+def test_members_is_one_except_for_the_ensemble_tables():
+    for who in GOOD:
+        assert new(who).members == 1, who
+    for who, table in _member_tables(3).items():
+        assert table.members == 3, who
+
+
+def test_table_inputs_are_the_views_run_handed_to_update():
+    """``forecast.table_inputs`` against what ``Forecaster.run`` spelt out per table kind: ``t`` and ``k`` for a table of
+    single states, ``t[::M]`` (and ``k[::M]``) for an ensemble table, the column only where the table takes one and the
+    run has one - the same addresses, shapes and strides, nothing copied"""
+    from paradis_model_amd.forecast import table_inputs
+    M = 3
+    truth = torch.arange(6 * 2 * 3 * 4 * 8, dtype=torch.float32).reshape(6, 2, 3, 4, 8)
+    clim_index = torch.arange(12, dtype=torch.int32).reshape(6, 2)
+    state = torch.zeros(6, 3, 4, 8)
+    view = lambda a: (a.data_ptr(), tuple(a.shape), a.stride(), a.dtype)      # noqa: E731
+    same = lambda a, b: view(a) == view(b)                                    # noqa: E731
+    tables = {**{who: new(who) for who in GOOD}, **_member_tables(M)}
+    for lead in range(2):
+        t, k = truth[:, lead], clim_index[:, lead]
+        for who, table in tables.items():
+            m = M if who in ("EnsembleCard", "ProbabilityTable") else 1
+            takes = who not in ("Spectra", "EnsembleCard")
+            for col in (k, None):
+                got = table_inputs(table, state, t, col)
+                assert len(got) == (3 if takes and col is not None else 2), (who, col is None)
+                assert got[0] is state
+                assert same(got[1], t[::m] if m > 1 else t), who
+                assert tuple(got[1].shape) == (6 // m, 3, 4, 8)
+                if len(got) == 3:
+                    assert same(got[2], k[::m] if m > 1 else k), who
+                    assert tuple(got[2].shape) == (6 // m,)
+    assert torch.equal(truth, torch.arange(6 * 2 * 3 * 4 * 8, dtype=torch.float32).reshape(6, 2, 3, 4, 8))
