@@ -735,6 +735,26 @@ int paradis_clim_quantile_packed(const uint16_t* codes, const float* params, con
                                  const int* cols, int C, const double* q_host, int Q, int min_count, float* out,
                                  int* flag, void* stream);
 
+/* ---- The SEEPS climatology (ABI 10, additive), csrc/quantile.hip: the same store, lists, tile, clamp flag and sort as
+ * paradis_clim_quantile, with another stage behind the sort.  The project's own restatement of the climatology of
+ * Rodwell et al. (2010); not pinned against any package.  With the m kept values v[0] <= .. <= v[m-1] of a cell, dry a
+ * finite float32 and wet_level a double in [0, 1] (both HOST values):
+ *   n_dry = #{ v[i] < dry }   (strict; -0.0 is +0.0 on both sides),   n_wet = m - n_dry
+ *   p1  = (float)((double)n_dry / (double)m)                                       NaN when m < min_count
+ *   pos = wet_level * (n_wet - 1),  lo = floor(pos),  hi = min(lo + 1, n_wet - 1),  frac = pos - lo
+ *   thr = (float)(v[n_dry + lo] + (v[n_dry + hi] - v[n_dry + lo]) * frac)          in double, uncontracted, one rounding;
+ *                                                                                  NaN when n_wet < 1 or m < min_count
+ * out is [2, K, C, H*W]: plane 0 p1, plane 1 thr.  K == 0 or C == 0 does nothing.  rc 1 before any HIP call for what
+ * paradis_clim_quantile refuses, a dry that is not finite and a wet_level outside [0, 1].
+ * Algorithmic HBM bytes: N*C*H*W*(4 | 2) read + 8*K*C*H*W written. */
+int paradis_clim_seeps(const float* store, int64_t T, int F, int H, int W, const int64_t* ptr, const int64_t* rows,
+                       int64_t N, int K, int max_entries, const int* cols, int C, float dry, double wet_level,
+                       int min_count, float* out, int* flag, void* stream);
+int paradis_clim_seeps_packed(const uint16_t* codes, const float* params, const int* domain, int64_t T, int F, int H,
+                              int W, const int64_t* ptr, const int64_t* rows, int64_t N, int K, int max_entries,
+                              const int* cols, int C, float dry, double wet_level, int min_count, float* out, int* flag,
+                              void* stream);
+
 /* ---- Zonal power spectra of forecast and truth (ABI 10, additive), csrc/spectrum.hip: at which scales a forecast has
  * gone wrong.  The project's own definition, in the spirit of WeatherBench-2's ZonalEnergySpectrum; not pinned against it.
  * One launch pair on `stream`, no host synchronisation, no memset or copy nodes, no atomics (bit-identical run to run);
@@ -916,6 +936,44 @@ int paradis_prob_update(const float* fc, int64_t fc_bs, const float* truth, int6
                         const int* clim_index, int K, const int* src_table, const float* thr_table, int64_t* acc_lead,
                         int64_t* n_samples_lead, void* ws, int G, int M, int T, int C, int S, int H, int W,
                         void* stream);
+
+/* ---- SEEPS, the three-category precipitation score (ABI 10, additive), csrc/seeps.hip: per lead, chosen channel and
+ * latitude row the 3x3 table of (forecast category, truth category), the masked cells and the row sums of the score
+ * split by the truth's category.  The project's own restatement of Rodwell et al. (2010), in the spirit of
+ * WeatherBench-2; not pinned against any package.  Three launches on `stream`, no host synchronisation, no memset or copy
+ * nodes, no atomics; no input is written.
+ *   fc / truth [B, C, H, W] fp32 in physical units, dense [C, H, W] states, fc_bs / truth_bs the batch strides in elements;
+ *   p1 / thr: the two planes of a SEEPS climatology (paradis_clim_seeps), cell p of slot k and output channel cs at
+ *   [k * clim_ks + cs * clim_cs + p] (strides in elements); clim_index int32 [B] (DEVICE): the slot of every sample;
+ *   chan_host int32 [Cs] (HOST, Cs <= paradis_seeps_max_channels() = 8): the state channel of output channel cs, checked
+ *   here and handed to the kernel as arguments - only these planes are read;
+ *   dry: the dry threshold; 0 < p_lo <= p_hi < 1: the bounds of p1 (all fp32, compared in fp32).
+ * cat(x) = 0 if x < dry, else 2 if x >= thr, else 1.  A cell is valid iff f, o, p1 and thr are finite, p_lo <= p1 <= p_hi
+ * and the sample's slot is in [0, K); masked iff all four are finite and the slot is in range but p1 is outside the
+ * bounds; anything else is counted nowhere, and nothing of an out-of-range slot is read.  Per valid cell, in double,
+ * uncontracted, p = (double)p1:
+ *   a = 1.0 / (1.0 - p),  b = 1.0 / p,  c = 3.0 / (2.0 + p)
+ *   M[cf][co] = {{0, a, 4.0 * a}, {b, 0, 3.0 * a}, {b + c, c, 0}},   s = 0.5 * M[cat(f)][cat(o)]
+ *   acc_real_lead: DEVICE double [Cs][H][3]: the sums of s over the row's valid cells whose truth is dry, light, heavy,
+ *   summed in a fixed order; the samples are folded in b order, (acc + s_0) + s_1 ..: two calls give the bits of one
+ *   call of the concatenated batch;
+ *   acc_int_lead: DEVICE int64 [Cs][H][10]: {n[cf][co] (cf-major), n_masked} += the counts (exact);
+ *   n_samples_lead: DEVICE int64 [1] += B.  Ordinary read-modify-writes (calls on one stream are ordered).
+ * A workgroup owns paradis_seeps_rows(W) (0 for W < 1) whole rows of one (sample, channel).  ws:
+ * paradis_seeps_ws_bytes(B, Cs, H, W) bytes, 8-byte aligned: double [B][Cs][H][3], then uint32 [B][Cs][H][10].  B == 0 or
+ * K == 0 does nothing.  rc 1 before any HIP call for: B or K < 0, C / Cs / H / W < 1, Cs above the maximum, a dry that is
+ * not finite, bounds that are not 0 < p_lo <= p_hi < 1, a NULL accumulator, ws or input, a channel outside [0, C),
+ * H W >= 2^31 - 8192, strides shorter than a state / a plane, a grid above the launch limit.
+ * W % 4 == 0 with 16-byte aligned bases and strides takes one 16-byte load per plane and quad of cells, anything else
+ * scalar loads: the same bits.  Algorithmic HBM bytes per cell of a channel: 16. */
+int paradis_seeps_max_channels(void);
+int paradis_seeps_rows(int W);
+size_t paradis_seeps_ws_bytes(int B, int Cs, int H, int W);
+int paradis_seeps_update(const float* fc, int64_t fc_bs, const float* truth, int64_t truth_bs, const float* p1,
+                         const float* thr, int64_t clim_ks, int64_t clim_cs, const int* clim_index, int K,
+                         const int* chan_host, int Cs, float dry, float p_lo, float p_hi, double* acc_real_lead,
+                         int64_t* acc_int_lead, int64_t* n_samples_lead, void* ws, int B, int C, int H, int W,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 """What the per-lead verification tables share - ``verify.Scorecard``, ``spectrum.Spectra``, ``events.EventTable``,
-``neighbourhood.FractionsTable``, ``ensemble.EnsembleCard`` and ``probability.ProbabilityTable``: the argument checks
-of their constructors and of ``update``, the one-slot climatology index and the single device read of ``result``.
+``neighbourhood.FractionsTable``, ``ensemble.EnsembleCard``, ``probability.ProbabilityTable`` and ``seeps.SeepsTable``:
+the argument checks of their constructors and of ``update``, the one-slot climatology index and the single device read
+of ``result``.
 
 Plain functions first; ``who`` is the class name that opens every message, so each table keeps its own words.  The small
 base class ``LeadTable`` holds what the checks need (``names``, ``C``, ``n_leads``, ``device``, ``H``, ``W``, ``bands``,

@@ -142,6 +142,8 @@ SIGNATURES = {
     "paradis_clim_quantile_cells": (I, [I]),
     "paradis_clim_quantile": (I, [P, L, I, I, I, P, P, L, I, I, P, I, P, I, I, P, P, P]),
     "paradis_clim_quantile_packed": (I, [P, P, P, L, I, I, I, P, P, L, I, I, P, I, P, I, I, P, P, P]),
+    "paradis_clim_seeps": (I, [P, L, I, I, I, P, P, L, I, I, P, I, F, D, I, P, P, P]),
+    "paradis_clim_seeps_packed": (I, [P, P, P, L, I, I, I, P, P, L, I, I, P, I, F, D, I, P, P, P]),
     "paradis_spectrum_rows": (I, []),
     "paradis_spectrum_fft_max_w": (I, []),
     "paradis_spectrum_direct_max_w": (I, []),
@@ -169,6 +171,10 @@ SIGNATURES = {
     "paradis_prob_counters": (I, [I, I]),
     "paradis_prob_ws_bytes": (S, [I, I, I, I, I, I]),
     "paradis_prob_update": (I, [P, L, P, L, P, P, I, P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "paradis_seeps_max_channels": (I, []),
+    "paradis_seeps_rows": (I, [I]),
+    "paradis_seeps_ws_bytes": (S, [I, I, I, I]),
+    "paradis_seeps_update": (I, [P, L, P, L, P, P, L, L, P, I, P, I, F, F, F, P, P, P, P, I, I, I, I, P]),
 }
 
 _missing = []

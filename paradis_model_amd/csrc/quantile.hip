@@ -12,8 +12,18 @@
 //
 // N*C*P*(4 | 2) B read, Q*K*C*P*4 B written; the work is the sort in LDS.  No atomics, no zero fill: bit-identical run
 // to run.
+//
+// The SEEPS climatology (paradis_clim_seeps[_packed]) is the same fill and the same sort with another stage behind them
+// (QT_SELECT_SEEPS, a compile-time choice of the one kernel).  With dry a finite float32 and wet_level in [0, 1]:
+//   n_dry = #{ v[i] < dry }  (strict: the lower bound of key(dry) among the sorted keys),  n_wet = m - n_dry
+//   p1  = (float)((double)n_dry / (double)m)                                      NaN when m < min_count
+//   pos = wet_level * (n_wet - 1),  lo = floor(pos),  hi = min(lo + 1, n_wet - 1),  frac = pos - lo
+//   thr = (float)(v[n_dry + lo] + (v[n_dry + hi] - v[n_dry + lo]) * frac)         NaN when n_wet < 1 or m < min_count
+// out is [2, K, C, P]: plane 0 p1, plane 1 thr.  tests/seeps_oracle.py restates it.
 #include "common.h"
 #include "store_reader.h"
+
+#include <cmath>
 
 #pragma clang fp contract(off)
 
@@ -30,6 +40,10 @@ namespace {
 constexpr int QT_THREADS = 256, QT_ROWS = 4, QT_MAX_CELLS = 64, QT_MAX_ENTRIES = 4096, QT_MAX_LEVELS = 8;
 constexpr int QT_LDS_BYTES = 128 * 1024, QT_WIDE_CELLS = 1024, QT_WIDE_BYTES = 64 * 1024;
 constexpr uint32_t QT_MISSING = 0xffffffffu;   // the image of a NaN pattern: above every finite value's key
+
+// what the stage behind the sort computes; its parameters travel in QtLevels either way
+constexpr int QT_SELECT_LEVELS = 0;   // lv.q[0 .. Q): the levels; out [Q, K, C, P]
+constexpr int QT_SELECT_SEEPS = 1;    // lv.q[0] = wet_level, lv.q[1] = (double)dry (exact); Q = 2 planes: out [2, K, C, P]
 
 struct QtLevels {
   double q[QT_MAX_LEVELS];
@@ -136,7 +150,7 @@ __device__ __forceinline__ void qt_block_steps(uint32_t* __restrict__ key, int c
 // QT_ROWS of a thread's items are in flight in front of the LDS writes.  (Entry-uniform waves, as in clim_mean, would
 // leave a 64-cell tile one row per wave-load; here a wave's load covers 64 / units rows, and rows[] and a packed
 // plane's (lo, s) are same-address loads.)
-template <class Reader, bool VEC>
+template <class Reader, bool VEC, int SELECT>
 __global__ void __launch_bounds__(QT_THREADS)
 clim_quantile_kernel(const Reader store, int64_t T, int F, int64_t P, const int64_t* __restrict__ ptr,
                      const int64_t* __restrict__ rows, int64_t N, int k0, int K, const int* __restrict__ cols, int C,
@@ -229,42 +243,83 @@ clim_quantile_kernel(const Reader store, int64_t T, int F, int64_t P, const int6
       }
   }
 
-  // ---- select: thread (level, cell); m = the position of the first missing key
-  const int n_sel = Q << cells_log2;
-  for (int i = tid; i < n_sel; i += QT_THREADS) {
-    const int cell = i & (cells - 1), qi = i >> cells_log2;
-    if (lo + cell >= P) continue;
-    const uint32_t* col = key + cell;
-    int a = 0, b = npk;
-    while (a < b) {
-      const int mid = (a + b) >> 1;
-      if (col[(size_t)mid << cells_log2] == QT_MISSING) b = mid;
-      else a = mid + 1;
-    }
-    const int m = a;
-    double q = lv.q[0];
+  // ---- select: m = the position of the first missing key
+  if constexpr (SELECT == QT_SELECT_LEVELS) {
+    // thread (level, cell)
+    const int n_sel = Q << cells_log2;
+    for (int i = tid; i < n_sel; i += QT_THREADS) {
+      const int cell = i & (cells - 1), qi = i >> cells_log2;
+      if (lo + cell >= P) continue;
+      const uint32_t* col = key + cell;
+      int a = 0, b = npk;
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (col[(size_t)mid << cells_log2] == QT_MISSING) b = mid;
+        else a = mid + 1;
+      }
+      const int m = a;
+      double q = lv.q[0];
 #pragma unroll
-    for (int j = 1; j < QT_MAX_LEVELS; ++j)
-      if (qi == j) q = lv.q[j];
-    float o = __builtin_nanf("");
-    if (m >= min_count) {                                         // min_count >= 1: m >= 1
-      const double pos = q * (double)(m - 1), fl = floor(pos), frac = pos - fl;
-      const int il = (int)fl, ih = il + 1 < m - 1 ? il + 1 : m - 1;
-      const double vl = qt_value(col[(size_t)il << cells_log2]), vh = qt_value(col[(size_t)ih << cells_log2]);
-      o = (float)(vl + (vh - vl) * frac);
+      for (int j = 1; j < QT_MAX_LEVELS; ++j)
+        if (qi == j) q = lv.q[j];
+      float o = __builtin_nanf("");
+      if (m >= min_count) {                                         // min_count >= 1: m >= 1
+        const double pos = q * (double)(m - 1), fl = floor(pos), frac = pos - fl;
+        const int il = (int)fl, ih = il + 1 < m - 1 ? il + 1 : m - 1;
+        const double vl = qt_value(col[(size_t)il << cells_log2]), vh = qt_value(col[(size_t)ih << cells_log2]);
+        o = (float)(vl + (vh - vl) * frac);
+      }
+      out[(((int64_t)qi * K + k) * C + c) * P + lo + cell] = o;
     }
-    out[(((int64_t)qi * K + k) * C + c) * P + lo + cell] = o;
+  } else {
+    // thread cell: both planes.  n_dry = the position of the first key >= key(dry) among the m kept (a missing key is
+    // above every finite value's, so the search needs no m)
+    const double wet_level = lv.q[0];
+    const uint32_t kdry = qt_key((float)lv.q[1]);
+    for (int cell = tid; cell < cells; cell += QT_THREADS) {
+      if (lo + cell >= P) continue;
+      const uint32_t* col = key + cell;
+      int a = 0, b = npk;
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (col[(size_t)mid << cells_log2] == QT_MISSING) b = mid;
+        else a = mid + 1;
+      }
+      const int m = a;
+      a = 0, b = m;
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (col[(size_t)mid << cells_log2] >= kdry) b = mid;
+        else a = mid + 1;
+      }
+      const int n_dry = a, n_wet = m - n_dry;
+      float p1 = __builtin_nanf(""), thr = __builtin_nanf("");
+      if (m >= min_count) {                                         // min_count >= 1: m >= 1
+        p1 = (float)((double)n_dry / (double)m);
+        if (n_wet >= 1) {
+          const double pos = wet_level * (double)(n_wet - 1), fl = floor(pos), frac = pos - fl;
+          const int il = (int)fl, ih = il + 1 < n_wet - 1 ? il + 1 : n_wet - 1;
+          const double vl = qt_value(col[(size_t)(n_dry + il) << cells_log2]);
+          const double vh = qt_value(col[(size_t)(n_dry + ih) << cells_log2]);
+          thr = (float)(vl + (vh - vl) * frac);
+        }
+      }
+      const int64_t at = ((int64_t)k * C + c) * P + lo + cell;
+      out[at] = p1;
+      out[(int64_t)K * C * P + at] = thr;
+    }
   }
 }
 
 PerDeviceOnce qt_lds_once;
 
-// the argument checks and the launches of both entry points
-template <class Reader>
+// the argument checks and the launches of the four entry points.  set_select(lv): the checks of the stage's own
+// parameters, behind the shared ones, and the fill of lv; Q: the planes of out
+template <int SELECT, class Reader, class SetSelect>
 int clim_quantile_launch(const char* name, const Reader& store, bool store_ok, bool store_vec, int64_t T, int F, int H,
                          int W, const int64_t* ptr, const int64_t* rows, int64_t N, int K, int max_entries,
-                         const int* cols, int C, const double* q_host, int Q, int min_count, float* out, int* flag,
-                         void* stream) {
+                         const int* cols, int C, bool select_ok, int Q, SetSelect&& set_select, int min_count,
+                         float* out, int* flag, void* stream) {
   PD_REQUIRE(T >= 1 && F >= 1 && H >= 1 && W >= 1 && K >= 0 && C >= 0, "%s: bad shape T=%lld F=%d H=%d W=%d K=%d C=%d",
              name, (long long)T, F, H, W, K, C);
   PD_REQUIRE(N >= 0, "%s: N=%lld list entries", name, (long long)N);
@@ -273,15 +328,13 @@ int clim_quantile_launch(const char* name, const Reader& store, bool store_ok, b
              QT_MAX_ENTRIES);
   PD_REQUIRE(min_count >= 1, "%s: min_count=%d, at least 1", name, min_count);
   if (K == 0 || C == 0 || Q == 0) return 0;
-  PD_REQUIRE(store_ok && ptr != nullptr && cols != nullptr && q_host != nullptr && out != nullptr && flag != nullptr,
-             "%s: store, ptr, cols, q, out and flag pointers required", name);
+  PD_REQUIRE(store_ok && ptr != nullptr && cols != nullptr && select_ok && out != nullptr && flag != nullptr,
+             "%s: store, ptr, cols, %sout and flag pointers required", name, SELECT == QT_SELECT_LEVELS ? "q, " : "");
   PD_REQUIRE(N == 0 || rows != nullptr, "%s: rows required for %lld entries", name, (long long)N);
   QtLevels lv;
   for (int i = 0; i < QT_MAX_LEVELS; ++i) lv.q[i] = 0.0;
-  for (int i = 0; i < Q; ++i) {
-    PD_REQUIRE(q_host[i] >= 0.0 && q_host[i] <= 1.0, "%s: level %d is %g, outside [0, 1]", name, i, q_host[i]);
-    lv.q[i] = q_host[i];
-  }
+  const int rc = set_select(lv);
+  if (rc != 0) return rc;
   const int64_t P = (int64_t)H * W;
   const int npad = qt_npad(max_entries), cells_log2 = qt_cells_log2(npad), cells = 1 << cells_log2;
   const int64_t tiles = ceil_div64(P, cells);
@@ -291,11 +344,12 @@ int clim_quantile_launch(const char* name, const Reader& store, bool store_ok, b
              (long long)per_slot);
   const size_t lds = (size_t)cells * npad * sizeof(uint32_t);
   const bool vec = P % 4 == 0 && cells % 4 == 0 && store_vec;
-  if (lds > 64 * 1024 && qt_lds_once.first()) {
-    const void* kernels[4] = {reinterpret_cast<const void*>(clim_quantile_kernel<FloatPlanes, true>),
-                              reinterpret_cast<const void*>(clim_quantile_kernel<FloatPlanes, false>),
-                              reinterpret_cast<const void*>(clim_quantile_kernel<PackedPlanes, true>),
-                              reinterpret_cast<const void*>(clim_quantile_kernel<PackedPlanes, false>)};
+  if (lds > 64 * 1024 && qt_lds_once.first()) {                     // every instantiation, whichever asks first
+#define QT_KERNELS_OF(R, V) reinterpret_cast<const void*>(clim_quantile_kernel<R, V, QT_SELECT_LEVELS>), \
+                            reinterpret_cast<const void*>(clim_quantile_kernel<R, V, QT_SELECT_SEEPS>)
+    const void* kernels[8] = {QT_KERNELS_OF(FloatPlanes, true), QT_KERNELS_OF(FloatPlanes, false),
+                              QT_KERNELS_OF(PackedPlanes, true), QT_KERNELS_OF(PackedPlanes, false)};
+#undef QT_KERNELS_OF
     for (const void* kn : kernels)
       if (hipFuncSetAttribute(kn, hipFuncAttributeMaxDynamicSharedMemorySize, QT_LDS_BYTES) != hipSuccess) {
         paradis_set_error("%s: cannot reserve LDS", name);
@@ -307,16 +361,38 @@ int clim_quantile_launch(const char* name, const Reader& store, bool store_ok, b
     const int64_t nk = K - k0 < slots_per_launch ? K - k0 : slots_per_launch;
     const dim3 grid((unsigned)(nk * per_slot)), block(QT_THREADS);
     if (vec)
-      hipLaunchKernelGGL((clim_quantile_kernel<Reader, true>), grid, block, lds, (hipStream_t)stream, store, T, F, P,
-                         ptr, rows, N, (int)k0, K, cols, C, (int)tiles, cells_log2, max_entries, lv, Q, min_count, out,
+      hipLaunchKernelGGL((clim_quantile_kernel<Reader, true, SELECT>), grid, block, lds, (hipStream_t)stream, store, T, F,
+                         P, ptr, rows, N, (int)k0, K, cols, C, (int)tiles, cells_log2, max_entries, lv, Q, min_count, out,
                          flag);
     else
-      hipLaunchKernelGGL((clim_quantile_kernel<Reader, false>), grid, block, lds, (hipStream_t)stream, store, T, F, P,
-                         ptr, rows, N, (int)k0, K, cols, C, (int)tiles, cells_log2, max_entries, lv, Q, min_count, out,
-                         flag);
+      hipLaunchKernelGGL((clim_quantile_kernel<Reader, false, SELECT>), grid, block, lds, (hipStream_t)stream, store, T,
+                         F, P, ptr, rows, N, (int)k0, K, cols, C, (int)tiles, cells_log2, max_entries, lv, Q, min_count,
+                         out, flag);
     PD_CHECK_LAUNCH(name);
   }
   return 0;
+}
+
+// the levels of paradis_clim_quantile[_packed]
+auto qt_set_levels(const char* name, const double* q_host, int Q) {
+  return [=](QtLevels& lv) -> int {
+    for (int i = 0; i < Q; ++i) {
+      PD_REQUIRE(q_host[i] >= 0.0 && q_host[i] <= 1.0, "%s: level %d is %g, outside [0, 1]", name, i, q_host[i]);
+      lv.q[i] = q_host[i];
+    }
+    return 0;
+  };
+}
+
+// the parameters of paradis_clim_seeps[_packed]
+auto qt_set_seeps(const char* name, float dry, double wet_level) {
+  return [=](QtLevels& lv) -> int {
+    PD_REQUIRE(std::isfinite(dry), "%s: the dry threshold is %g, not finite", name, (double)dry);
+    PD_REQUIRE(wet_level >= 0.0 && wet_level <= 1.0, "%s: wet_level is %g, outside [0, 1]", name, wet_level);
+    lv.q[0] = wet_level;
+    lv.q[1] = (double)dry;
+    return 0;
+  };
 }
 
 }  // namespace
@@ -331,15 +407,37 @@ extern "C" int paradis_clim_quantile_cells(int max_entries) {
 extern "C" int paradis_clim_quantile(const float* store, int64_t T, int F, int H, int W, const int64_t* ptr,
                                      const int64_t* rows, int64_t N, int K, int max_entries, const int* cols, int C,
                                      const double* q_host, int Q, int min_count, float* out, int* flag, void* stream) {
-  return clim_quantile_launch("clim_quantile", FloatPlanes{store}, store != nullptr, aligned16(store), T, F, H, W, ptr,
-                              rows, N, K, max_entries, cols, C, q_host, Q, min_count, out, flag, stream);
+  return clim_quantile_launch<QT_SELECT_LEVELS>("clim_quantile", FloatPlanes{store}, store != nullptr, aligned16(store),
+                                                T, F, H, W, ptr, rows, N, K, max_entries, cols, C, q_host != nullptr, Q,
+                                                qt_set_levels("clim_quantile", q_host, Q), min_count, out, flag, stream);
 }
 
 extern "C" int paradis_clim_quantile_packed(const uint16_t* codes, const float* params, const int* domain, int64_t T,
                                             int F, int H, int W, const int64_t* ptr, const int64_t* rows, int64_t N,
                                             int K, int max_entries, const int* cols, int C, const double* q_host, int Q,
                                             int min_count, float* out, int* flag, void* stream) {
-  return clim_quantile_launch("clim_quantile_packed", PackedPlanes{codes, params, domain},
-                              codes != nullptr && params != nullptr && domain != nullptr, aligned8(codes), T, F, H, W,
-                              ptr, rows, N, K, max_entries, cols, C, q_host, Q, min_count, out, flag, stream);
+  return clim_quantile_launch<QT_SELECT_LEVELS>("clim_quantile_packed", PackedPlanes{codes, params, domain},
+                                                codes != nullptr && params != nullptr && domain != nullptr,
+                                                aligned8(codes), T, F, H, W, ptr, rows, N, K, max_entries, cols, C,
+                                                q_host != nullptr, Q, qt_set_levels("clim_quantile_packed", q_host, Q),
+                                                min_count, out, flag, stream);
+}
+
+extern "C" int paradis_clim_seeps(const float* store, int64_t T, int F, int H, int W, const int64_t* ptr,
+                                  const int64_t* rows, int64_t N, int K, int max_entries, const int* cols, int C,
+                                  float dry, double wet_level, int min_count, float* out, int* flag, void* stream) {
+  return clim_quantile_launch<QT_SELECT_SEEPS>("clim_seeps", FloatPlanes{store}, store != nullptr, aligned16(store), T,
+                                               F, H, W, ptr, rows, N, K, max_entries, cols, C, true, 2,
+                                               qt_set_seeps("clim_seeps", dry, wet_level), min_count, out, flag, stream);
+}
+
+extern "C" int paradis_clim_seeps_packed(const uint16_t* codes, const float* params, const int* domain, int64_t T, int F,
+                                         int H, int W, const int64_t* ptr, const int64_t* rows, int64_t N, int K,
+                                         int max_entries, const int* cols, int C, float dry, double wet_level,
+                                         int min_count, float* out, int* flag, void* stream) {
+  return clim_quantile_launch<QT_SELECT_SEEPS>("clim_seeps_packed", PackedPlanes{codes, params, domain},
+                                               codes != nullptr && params != nullptr && domain != nullptr,
+                                               aligned8(codes), T, F, H, W, ptr, rows, N, K, max_entries, cols, C, true,
+                                               2, qt_set_seeps("clim_seeps_packed", dry, wet_level), min_count, out, flag,
+                                               stream);
 }

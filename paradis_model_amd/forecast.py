@@ -208,10 +208,10 @@ def chunk_plan(forecast_steps: int, output_frequency: int, write_every_n: Option
 
 
 # ---------------------------------------------------------------------------------- the predict loop
-def _passed(scorecard, spectra, events, fractions, ensemble=None, probability=None) -> list:
+def _passed(scorecard, spectra, events, fractions, ensemble=None, probability=None, seeps=None) -> list:
     """the verification tables given to ``run`` (``_leadtable.LeadTable``: each brings its phrases, its ``members`` and
     whether its ``update`` takes ``clim_index``), in the order of their refusals and of their launches"""
-    return [t for t in (scorecard, spectra, events, fractions, ensemble, probability) if t is not None]
+    return [t for t in (scorecard, spectra, events, fractions, ensemble, probability, seeps) if t is not None]
 
 
 def table_inputs(table, state, truth, clim_col) -> tuple:
@@ -244,7 +244,7 @@ class Forecaster:
     validation batch's ``true_data``) and goes through the same ``postprocess`` into a scratch state first.  A scorecard
     without ``truth``, or a truth of another ``n_stored``, is refused before the rollout starts.
 
-    Five more tables go beside or without a scorecard, each under its own keyword, any subset of the six in one run.
+    Six more tables go beside or without a scorecard, each under its own keyword, any subset of the seven in one run.
     The rule is one (``table_inputs``): the same finished state and the same truth state (one ``postprocess`` of a
     model-space truth serves all) go through each ``table.update`` at lead ``k``, with the ``clim_index`` column where
     the table takes one, on the main stream in the order below, in front of the same event.  An ensemble table
@@ -260,6 +260,8 @@ class Forecaster:
         ``fractions=<neighbourhood.FractionsTable>``          three launches
         ``ensemble=<ensemble.EnsembleCard>``                  one launch pair; ``members``; takes no ``clim_index``
         ``probability=<probability.ProbabilityTable>``        one launch pair; ``members``
+        ``seeps=<seeps.SeepsTable>``                          three launches; ``clim_index``: the slots of its own
+                                                              ``SeepsClimatology`` (one plan serves every table of a run)
 
     ``run(..., encoder=<encode.EncodeSpec>, init=<(state [B, 1, C, H, W], dew [B, 1, L, H, W] or None) or None>)``: a
     flushed chunk is regrouped into the writer's named variables and BitRounded on the device (``encode.encode_chunk``,
@@ -294,12 +296,12 @@ class Forecaster:
         return ring.pin() if pinned else ring
 
     def _check_verification(self, scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W, spectra=None,
-                            events=None, fractions=None, ensemble=None, probability=None):
-        """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=..., ensemble=..., probability=...)``,
-        before the rollout starts;
+                            events=None, fractions=None, ensemble=None, probability=None, seeps=None):
+        """the refusals of ``run(scorecard=..., spectra=..., events=..., fractions=..., ensemble=..., probability=...,
+        seeps=...)``, before the rollout starts;
         returns the forecaster's ``[B, 1, C, H, W]`` scratch tensor for a model-space truth (``truth_normalized=True``),
         else None"""
-        tables = _passed(scorecard, spectra, events, fractions, ensemble, probability)
+        tables = _passed(scorecard, spectra, events, fractions, ensemble, probability, seeps)
         if not tables:
             if truth is not None or clim_index is not None or truth_normalized:
                 raise ValueError("Forecaster.run: truth, truth_normalized and clim_index go with a scorecard")
@@ -358,8 +360,8 @@ class Forecaster:
     def run(self, input_data, forcings, constants, on_chunk: Optional[Callable],
             forecast_steps: Optional[int] = None, *, scorecard=None, truth: Optional[torch.Tensor] = None,
             truth_normalized: bool = False, clim_index: Optional[torch.Tensor] = None, encoder=None, init=None,
-            spectra=None, events=None, fractions=None, ensemble=None, probability=None):
-        tables = _passed(scorecard, spectra, events, fractions, ensemble, probability)
+            spectra=None, events=None, fractions=None, ensemble=None, probability=None, seeps=None):
+        tables = _passed(scorecard, spectra, events, fractions, ensemble, probability, seeps)
         for t in tables:                                     # (host-side refusals, in front of the device checks)
             if truth is None:
                 raise ValueError(f"Forecaster.run: {t.NEEDS} truth [B, n_stored, C, H, W] on the device")
@@ -372,7 +374,7 @@ class Forecaster:
         B, _, _, H, W = input_data.shape
         C, L = self.spec.num_channels, self.spec.num_levels
         truth_phys = self._check_verification(scorecard, truth, truth_normalized, clim_index, B, n_stored, C, H, W,
-                                              spectra, events, fractions, ensemble, probability)
+                                              spectra, events, fractions, ensemble, probability, seeps)
         init = self._check_encoder(encoder, init, B, C, L, H, W)
         sizes = [p.flush[1] for p in plan if p.flush is not None]         # per chunk its number of states
         n_chunk, sizes = max(sizes), iter(sizes)
@@ -407,7 +409,7 @@ class Forecaster:
                         postprocess(t, self.spec, self.lat_deg, self.lon_deg, truth_phys, 0)
                         t = truth_phys[:, 0]
                     k = None if clim_index is None else clim_index[:, i_stored]
-                    for table in tables:         # (scorecard, .., fractions, ensemble, probability: the launch order)
+                    for table in tables:         # (scorecard, .., ensemble, probability, seeps: the launch order)
                         table.update(i_stored, *table_inputs(table, d[:, p.slot], t, k))
                 i_stored += 1
             if p.flush is not None:
