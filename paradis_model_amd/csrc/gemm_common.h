@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <initializer_list>
+#include <type_traits>
 #include "common.h"
 
 struct GemmArgs {
@@ -27,6 +28,7 @@ struct GemmArgs {
   int act;
   int stagger;                // start-up skew between co-resident workgroups, in units of 512 cycles
   float* rowsum;              // wgrad only: [nbatch][M] partial row sums of A (= bias gradient), or NULL
+  int generic_epilogue;       // split wgrad only: every tile ends in gemm_epilogue (PARADIS_GEMM_EPILOGUE=generic)
   // low-rank bias map applied on the fly: acc[m,n] += sum_c pw[c*M + m] * m8[c*N + n]  (M % 4 == 0)
   const float* m8; const float* pw; int cin;
   // f16x2 scheme: where the operands' max |value| comes from.  a_amax: one word (bits of max |A|, weight
@@ -486,6 +488,32 @@ constexpr int simgp(int np) { return np * 2 * SCHP; }
 #ifndef SPLIT_SIGNED_WGRAD    // (the slab alternation of the weight gradient alone)
 #define SPLIT_SIGNED_WGRAD SPLIT_SIGNED
 #endif
+// The sign as a compile-time property of the k-loop (bf16x3 kernels): the sign of a staging wave (forward / data gradient:
+// bit 6 of its column) or workgroup (weight gradient: the slab's parity) never changes during a launch, so the wave picks
+// ONE of two complete copies of prologue and k-loop ahead of the loop; the negated copy splits -x through source modifiers
+// (split8s<true>) where the single loop spends eight v_xor per thread and k-tile (flip8).  Each copy keeps one basic block
+// per step.  The weight gradient likewise keeps its fused row sums to a loop copy of the workgroups that store them, forms
+// its load addresses from a scalar base and one 32-bit lane offset, and stores interior tiles through
+// split_epilogue_interior.  -DSPLIT_SIGN_LOOPS=0 restores the v_xor loops and everything else of the single-loop kernels
+// (A/B builds); the parts can be switched one at a time.
+#ifndef SPLIT_SIGN_LOOPS
+#define SPLIT_SIGN_LOOPS 1
+#endif
+#ifndef SPLIT_SIGN_LOOPS_FWD         // forward / data gradient: sign copies of pw_gemm_split_wide_kernel<2, 3, EPI>
+#define SPLIT_SIGN_LOOPS_FWD SPLIT_SIGN_LOOPS
+#endif
+#ifndef SPLIT_SIGN_LOOPS_WGRAD       // weight gradient: sign copies
+#define SPLIT_SIGN_LOOPS_WGRAD SPLIT_SIGN_LOOPS
+#endif
+#ifndef SPLIT_WGRAD_ROWSUM_LOOP      // weight gradient: row-sum adds only in the copy of the workgroups that store them
+#define SPLIT_WGRAD_ROWSUM_LOOP SPLIT_SIGN_LOOPS
+#endif
+#ifndef SPLIT_WGRAD_SADDR            // weight gradient: scalar base + 32-bit lane offset
+#define SPLIT_WGRAD_SADDR SPLIT_SIGN_LOOPS
+#endif
+#ifndef SPLIT_WGRAD_EPILOGUE         // weight gradient: interior tiles through split_epilogue_interior<EP_ON>
+#define SPLIT_WGRAD_EPILOGUE SPLIT_SIGN_LOOPS
+#endif
 // sign bit of the staging thread's activation column (column = tid & 127 of a 128-column tile)
 __device__ __forceinline__ uint32_t split_flip_mask(int col) { return SPLIT_SIGNED && (col & 64) ? 0x80000000u : 0u; }
 __device__ __forceinline__ void flip8(float (&y)[8], const float (&x)[8], uint32_t mask) {
@@ -569,6 +597,29 @@ __device__ __forceinline__ void split8(const float (&x)[8], u32x4& h, u32x4& m, 
   l = (u32x4){ll[0], ll[1], ll[2], ll[3]};
 }
 
+// the planes of x (FLIP = false) or of -x (true): -x splits exactly into (-h, -m, -l); the negations are written in the
+// expressions, where they fold into the source modifiers of v_cvt_pk_bf16_f32 and v_sub_f32
+template <bool FLIP>
+__device__ __forceinline__ void split8s(const float (&x)[8], u32x4& h, u32x4& m, u32x4& l) {
+  if constexpr (!FLIP) {
+    split8(x, h, m, l);
+  } else {
+    uint32_t hh[4], mm[4], ll[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float x0 = x[2 * i], x1 = x[2 * i + 1];
+      // (hipcc folds the negation into v_sub_f32 but not into the conversion: spelled out, or it costs the v_xor again)
+      asm("v_cvt_pk_bf16_f32 %0, -%1, -%2" : "=v"(hh[i]) : "v"(x0), "v"(x1));
+      const float r0 = (-x0) - __uint_as_float(hh[i] << 16), r1 = (-x1) - __uint_as_float(hh[i] & 0xffff0000u);
+      mm[i] = pack_bf16(r0, r1);
+      ll[i] = pack_bf16(r0 - __uint_as_float(mm[i] << 16), r1 - __uint_as_float(mm[i] & 0xffff0000u));
+    }
+    h = (u32x4){hh[0], hh[1], hh[2], hh[3]};
+    m = (u32x4){mm[0], mm[1], mm[2], mm[3]};
+    l = (u32x4){ll[0], ll[1], ll[2], ll[3]};
+  }
+}
+
 // eight values rounded to bf16 (the one plane of PARADIS_GEMM_BF16)
 __device__ __forceinline__ u32x4 round8(const float (&x)[8]) {
   return (u32x4){pack_bf16(x[0], x[1]), pack_bf16(x[2], x[3]), pack_bf16(x[4], x[5]), pack_bf16(x[6], x[7])};
@@ -644,6 +695,160 @@ __device__ __forceinline__ void split_unscale(f32x16 (&acc)[2][2], float inv_a, 
       for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] * inv_a) * inv_b;
 }
 
+// ---- the interior-tile epilogue of the six-product (bf16x3) kernels, one instantiation per option set ------------------------
+// gemm_epilogue (above) decides every option at run time and waits for each operand tensor of each group of eight values
+// on its own.  Here the option set EPI is a compile-time bit set, and per element the operations, their order and their
+// contraction are gemm_epilogue's, so the results are the same bits.  Two kernels use it: the 128 x 256 forward /
+// data-gradient kernel with the sets a training step launches (SPLIT_WIDE_EPI in gemm_split.hip), and the weight-gradient
+// kernel below with EP_ON alone - a slab or dW tile is a plain store.  Everything else, ragged tiles included, keeps
+// gemm_epilogue.
+//   * a wave walks its 64 x 64 block as eight groups (tm, h, tn) of eight rows x 64 lanes; all operand loads of group
+//     g + 1 (map, zmul, res) are issued before the arithmetic and the stores of group g, into the registers the k-loop
+//     has released, and waited for by count (the stores count as well: vmcnt retires in order);
+//   * loads and stores take the saddr form - a scalar row pointer plus ONE 32-bit lane offset ((4 lh ldc + li) x 4 bytes;
+//     the second 32-column tile sits in the instruction's immediate offset) - instead of a 64-bit vector address each;
+//   * bias[m] and sigmoid(gate[m]) are per-row values: lane l of a wave fetches row l of the wave's 64 rows once (one
+//     expf and one division per lane and tile instead of 64), and a pair of groups picks its eight rows with ds_bpermute.
+enum : int { EP_ON = 1, EP_BIAS = 2, EP_MAP = 4, EP_ZOUT = 8, EP_SILU = 16, EP_ZMUL = 32, EP_RES = 64, EP_GATE = 128 };
+
+template <int OFF>
+__device__ __forceinline__ void ep_load(float& x, uint32_t voff, const float* p) {
+  asm volatile("global_load_dword %0, %1, %2 offset:%3" : "=&v"(x) : "v"(voff), "s"(p), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void ep_store(float x, uint32_t voff, float* p) {
+  asm volatile("global_store_dword %0, %1, %2 offset:%3" :: "v"(voff), "v"(x), "s"(p), "n"(OFF) : "memory");
+}
+// at most N younger vector-memory operations outstanding; the registers waited for are INPUTS (see USE_X in gemm_split.hip)
+template <int N>
+__device__ __forceinline__ void ep_wait(const float (&a)[8]) {
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]),
+               "v"(a[7]) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int N>
+__device__ __forceinline__ void ep_wait(const float (&a)[8], const float (&b)[8]) {
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]),
+               "v"(a[7]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int N>
+__device__ __forceinline__ void ep_wait(float a, float b) {
+  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a), "v"(b) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ float ep_row(float rowvec, int addr) {      // rowvec of lane addr / 4
+  return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(rowvec)));
+}
+template <class T>
+__device__ __forceinline__ T* ep_uniform(T* p) {      // wave-uniform by construction: pin it to scalar registers
+  const uint64_t a = reinterpret_cast<uint64_t>(p);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
+}
+
+template <int EPI>
+__device__ __forceinline__ void split_epilogue_interior(const GemmArgs& g, f32x16 (&acc)[2][2], int bz, int m0, int n0,
+                                                        int wm, int wn, int li, int lh) {
+  constexpr bool BIAS = EPI & EP_BIAS, MAP = EPI & EP_MAP, ZOUT = EPI & EP_ZOUT, SILU = EPI & EP_SILU, ZMUL = EPI & EP_ZMUL,
+                 RES = EPI & EP_RES, GATE = EPI & EP_GATE;
+  static_assert(!(GATE && !RES) && !(ZMUL && (SILU || ZOUT)), "no such epilogue");
+  // operand tensors of a group, their slots in the load buffers, loads / stores per group
+  constexpr int NT = MAP + ZMUL + RES, I_MAP = 0, I_ZM = MAP, I_RES = MAP + ZMUL;
+  static_assert(NT <= 2, "a third operand tensor needs a third ep_wait");
+  constexpr int L = 8 * NT, S = 8 * (1 + ZOUT);
+  const int wrow = __builtin_amdgcn_readfirstlane(m0 + wm * 64), wcol = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
+  const int64_t ld = g.ldc, tile = (int64_t)wrow * ld + wcol;
+  float* const Cs = ep_uniform(g.C + (int64_t)bz * g.c_bs + tile);
+  float* const zos = ZOUT ? ep_uniform(g.zout + (int64_t)bz * g.zout_bs + tile) : nullptr;
+  const float* const mps = MAP ? ep_uniform(g.map + tile) : nullptr;
+  const float* const zms = ZMUL ? ep_uniform(g.zmul + (int64_t)bz * g.zmul_bs + tile) : nullptr;
+  const float* const rss = RES ? ep_uniform(g.res + (int64_t)bz * g.res_bs + tile) : nullptr;
+  const uint32_t voff = ((uint32_t)(4 * lh) * (uint32_t)ld + (uint32_t)li) * 4u;      // (host: ldc < 2^26)
+  const int radr = 16 * lh;                                   // ds_bpermute address of row 4 lh of the wave's 64
+  // group gi = (tm, h, tn); element q sits in row tm 32 + (q & 3) + 8 (2 h + (q >> 2)) (+ 4 lh) of the wave's block
+  auto rowof = [](int gi, int q) constexpr { return (gi >> 2) * 32 + (q & 3) + 8 * (2 * ((gi >> 1) & 1) + (q >> 2)); };
+
+  float bv = 0.f, gv = 0.f;             // lane l: bias / gate of row wrow + l
+  float buf[2][NT ? NT : 1][8];
+  auto issue = [&](auto G) __attribute__((always_inline)) {
+    constexpr int gi = decltype(G)::value, OFF = (gi & 1) * 128;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int64_t ro = (int64_t)rowof(gi, q) * ld;
+      if constexpr (MAP) ep_load<OFF>(buf[gi & 1][I_MAP][q], voff, mps + ro);
+      if constexpr (ZMUL) ep_load<OFF>(buf[gi & 1][I_ZM][q], voff, zms + ro);
+      if constexpr (RES) ep_load<OFF>(buf[gi & 1][I_RES][q], voff, rss + ro);
+    }
+  };
+  float br[8], gr[8];                   // the rows of the current (tm, h): picked at tn = 0, used by both column tiles
+  if constexpr (BIAS) ep_load<0>(bv, (uint32_t)(32 * lh + li) * 4u, ep_uniform(g.bias + wrow));
+  if constexpr (GATE) ep_load<0>(gv, (uint32_t)(32 * lh + li) * 4u, ep_uniform(g.gate + wrow));
+  if constexpr (NT > 0) issue(std::integral_constant<int, 0>{});
+  __builtin_amdgcn_sched_barrier(0);
+
+  auto group = [&](auto G) __attribute__((always_inline)) {
+    constexpr int gi = decltype(G)::value, tm = gi >> 2, h = (gi >> 1) & 1, tn = gi & 1, OFF = tn * 128, b = gi & 1;
+    if constexpr (NT > 0 && gi < 7) {
+      issue(std::integral_constant<int, gi + 1>{});
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (gi == 0 && (BIAS || GATE)) {
+      ep_wait<NT ? 2 * L : 0>(bv, gv);       // younger: the loads of groups 0 and 1
+      if constexpr (GATE) gv = gate_sigmoid(gv);
+    }
+    if constexpr (tn == 0 && (BIAS || GATE)) {      // eight (sixteen) picks back to back, one counted LDS wait each
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        if constexpr (BIAS) br[q] = ep_row(bv, radr + 4 * rowof(gi, q));
+        if constexpr (GATE) gr[q] = ep_row(gv, radr + 4 * rowof(gi, q));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // younger than this group's loads: the stores of the group before, the loads of the group after
+    constexpr int YOUNGER = (gi < 7 ? L : 0) + (gi > 0 ? S : 0);
+    if constexpr (NT == 1) ep_wait<YOUNGER>(buf[b][0]);
+    if constexpr (NT == 2) ep_wait<YOUNGER>(buf[b][0], buf[b][1]);
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = acc[tm][tn][8 * h + q];
+    if constexpr (BIAS) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] += br[q];
+    }
+    if constexpr (MAP) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] += buf[b][I_MAP][q];
+    }
+    if constexpr (ZOUT) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) ep_store<OFF>(v[q], voff, zos + (int64_t)rowof(gi, q) * ld);
+    }
+    if constexpr (ZMUL) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] *= act_grad(buf[b][I_ZM][q], PARADIS_ACT_SILU);
+    } else if constexpr (SILU) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = act_apply(v[q], PARADIS_ACT_SILU);
+    }
+    if constexpr (RES) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const float r = buf[b][I_RES][q];
+        if constexpr (GATE) v[q] = fmaf(gr[q], v[q] - r, r);
+        else v[q] += r;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) ep_store<OFF>(v[q], voff, Cs + (int64_t)rowof(gi, q) * ld);
+    __builtin_amdgcn_sched_barrier(0);      // (a group's arithmetic stays behind the stores of the group before)
+  };
+  group(std::integral_constant<int, 0>{}); group(std::integral_constant<int, 1>{});
+  group(std::integral_constant<int, 2>{}); group(std::integral_constant<int, 3>{});
+  group(std::integral_constant<int, 4>{}); group(std::integral_constant<int, 5>{});
+  group(std::integral_constant<int, 6>{}); group(std::integral_constant<int, 7>{});
+}
+
 // ---- the weight-gradient kernel of the split schemes: gemm_split.hip launches NP = 3 and 2, gemm_amp_wgrad.hip NP = 1 ---
 // wgrad: dW[M,N'] = sum over (sample, p) A[m][p] B[n][p], both operands p-contiguous fp32, both split
 // in registers.  Thread t stages 8 consecutive p of row t>>1 (k-half t&1) of each operand.
@@ -654,10 +859,19 @@ __device__ __forceinline__ void split_unscale(f32x16 (&acc)[2][2], float inv_a, 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // (A soft rendezvous of a K-range slab's tiles - round 5: FETCH_SIZE 8.48 -> 4.06 GB per launch at 128 x 256, kernel 13 %
 //  slower - was measured and removed: DESIGN_HISTORY.md section 4.1d, profiles/r05_wgrad_rendezvous.txt.)
-template <int NP>
+// A32 (bf16x3 only; the host's choice, split_wgrad_a32): both operands' tile rows lie within 2^31 bytes of the tile's first
+// row, so a load address is a scalar pointer (tile row 0 of the current sample and k-tile, advanced on the scalar unit)
+// plus one constant 32-bit lane offset - no 64-bit vector address arithmetic in the loop.
+template <int NP, int A32 = 0>
 __global__ void __launch_bounds__(256, 3)
 pw_gemm_wgrad_split_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  static_assert(A32 == 0 || NP == 3, "the scalar-base loads exist in the bf16x3 instantiation only");
+  constexpr bool SADDR = A32 != 0 && SPLIT_WGRAD_SADDR;
+  // loop copies (bf16x3): sign 0 / 1 = plain / negated at compile time, row sums 0 / 1 = absent / present; 2 = decided
+  // by run-time values inside the one loop, as in the two-plane and one-plane instantiations
+  constexpr bool SIGN_COPIES = NP == 3 && SPLIT_SIGN_LOOPS_WGRAD && SPLIT_SIGNED_WGRAD;
+  constexpr bool ROWSUM_COPIES = NP == 3 && SPLIT_WGRAD_ROWSUM_LOOP;
   constexpr int SIMGP = simgp(NP);
   u32x4* img = reinterpret_cast<u32x4*>(lds);        // [2 stages][A|B][SIMGP]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -671,31 +885,37 @@ pw_gemm_wgrad_split_kernel(GemmArgs g) {
     const int q = nwg >> 3, r = nwg & 7, xcd = id & 7;
     L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
   }
-  const int mt = L % MT, nt = (L / MT) % NT, bz = L / (MT * NT);
+  int mt = L % MT, nt = (L / MT) % NT, bz = L / (MT * NT);
+  if constexpr (SIGN_COPIES || ROWSUM_COPIES || SADDR) {
+    // (uniform, but divided on the vector unit: what the loop copies are chosen by, and what the epilogue keeps through
+    //  them, belongs in scalar registers)
+    mt = __builtin_amdgcn_readfirstlane(mt); nt = __builtin_amdgcn_readfirstlane(nt); bz = __builtin_amdgcn_readfirstlane(bz);
+  }
   const int m0 = mt * BM, n0 = nt * BN;
   const int KT = g.K / SBK;
   const int64_t total = (int64_t)g.inner * KT;
-  const int t_begin = (int)(total * bz / g.nbatch);
-  const int T = (int)(total * (bz + 1) / g.nbatch) - t_begin;
-
-  const int srow = tid >> 1, sh = tid & 1;
-  const float* Ag = g.A + (int64_t)min(m0 + srow, g.M - 1) * g.lda + sh * 8;
-  const float* Bg = g.B + (int64_t)min(n0 + srow, g.N - 1) * g.ldb + sh * 8;
+  int t_begin = (int)(total * bz / g.nbatch);
+  int T = (int)(total * (bz + 1) / g.nbatch) - t_begin;
+  if constexpr (SADDR) {      // (uniform, but divided on the vector unit: the loop's tile counters belong in scalar registers)
+    t_begin = __builtin_amdgcn_readfirstlane(t_begin);
+    T = __builtin_amdgcn_readfirstlane(T);
+  }
 
   // (sample, k-tile) of the next tile to fetch, advanced incrementally
-  int f_ib = t_begin / KT, f_kt = t_begin - f_ib * KT;
+  int f_ib0 = t_begin / KT, f_kt0 = t_begin - f_ib0 * KT;
+  // SADDR: row 0 of the tile at (sample, k-tile); a thread adds the byte offset of its row (run below)
+  const float* sa0 = nullptr;
+  const float* sb0 = nullptr;
+  int64_t wrap_a = 0, wrap_b = 0;       // what a step to the next sample's first k-tile adds on top of SBK
+  if constexpr (SADDR) {
+    f_ib0 = __builtin_amdgcn_readfirstlane(f_ib0);
+    f_kt0 = __builtin_amdgcn_readfirstlane(f_kt0);
+    sa0 = ep_uniform(g.A + (int64_t)m0 * g.lda + (int64_t)f_ib0 * g.a_is + (int64_t)f_kt0 * SBK);
+    sb0 = ep_uniform(g.B + (int64_t)n0 * g.ldb + (int64_t)f_ib0 * g.b_is + (int64_t)f_kt0 * SBK);
+    wrap_a = g.a_is - (int64_t)KT * SBK;
+    wrap_b = g.b_is - (int64_t)KT * SBK;
+  }
   struct Regs { f32x4 a0, a1, b0, b1; };
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  Regs r0{zero4, zero4, zero4, zero4}, r1 = r0;   // defined values: the surplus split of a one-tile range reads r1
-  auto fetch = [&](Regs& r) __attribute__((always_inline)) {
-    const float* a = Ag + (int64_t)f_ib * g.a_is + (int64_t)f_kt * SBK;
-    const float* b = Bg + (int64_t)f_ib * g.b_is + (int64_t)f_kt * SBK;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r.a0) : "v"(a) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=&v"(r.a1) : "v"(a) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r.b0) : "v"(b) : "memory");
-    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=&v"(r.b1) : "v"(b) : "memory");
-    if (++f_kt == KT) { f_kt = 0; ++f_ib; }
-  };
   // at most N younger vector-memory operations outstanding; registers as asm inputs (see USE_X)
 #define USE_R(r, N) do { asm volatile("s_waitcnt vmcnt(" #N ")" :: "v"(r.a0), "v"(r.a1), "v"(r.b0), "v"(r.b1) : "memory"); \
                          __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -709,19 +929,29 @@ pw_gemm_wgrad_split_kernel(GemmArgs g) {
   // the offset of the MFMA's accumulator alignment (see "sign checkerboard") cancels between an element's slabs
   const uint32_t slab_flip = (SPLIT_SIGNED_WGRAD && (bz & 1)) ? 0x80000000u : 0u;      // workgroup-uniform
   if constexpr (NP == 2) sc_a = __uint_as_float(__float_as_uint(sc_a) ^ slab_flip);
-  auto split_store = [&](const Regs& r, int st, bool keep) __attribute__((always_inline)) {
+  // SG / RS: the loop copy's sign and row-sum modes (see above)
+  // (o0: the thread's chunk in the A image of stage 0)
+  auto split_store = [&](auto SG, auto RS, const Regs& r, u32x4* o0, int st, bool keep) __attribute__((always_inline)) {
+    constexpr int sg = decltype(SG)::value, rsm = decltype(RS)::value;
     const float xa[8] = {r.a0.x, r.a0.y, r.a0.z, r.a0.w, r.a1.x, r.a1.y, r.a1.z, r.a1.w};
     const float xb[8] = {r.b0.x, r.b0.y, r.b0.z, r.b0.w, r.b1.x, r.b1.y, r.b1.z, r.b1.w};
     // bias gradient: row sums of the staged dY values (a select, not a product: the surplus split of the
     // last tile works on stale registers that may hold NaNs)
-    const float add = ((xa[0] + xa[1]) + (xa[2] + xa[3])) + ((xa[4] + xa[5]) + (xa[6] + xa[7]));
-    rs += keep ? add : 0.f;
-    u32x4* o = img + st * 2 * SIMGP + sh * SCHP + srow;
+    if constexpr (rsm != 0) {
+      const float add = ((xa[0] + xa[1]) + (xa[2] + xa[3])) + ((xa[4] + xa[5]) + (xa[6] + xa[7]));
+      rs += keep ? add : 0.f;
+    }
+    u32x4* o = o0 + st * 2 * SIMGP;
     if constexpr (NP == 3) {
       u32x4 ha, ma, la, hb, mb, lb;
-      float xs[8];
-      flip8(xs, xa, slab_flip);    // sign alternation by slab: odd K-ranges accumulate -dW
-      split8(xs, ha, ma, la);
+      // sign alternation by slab: odd K-ranges accumulate -dW
+      if constexpr (sg == 2) {
+        float xs[8];
+        flip8(xs, xa, slab_flip);
+        split8(xs, ha, ma, la);
+      } else {
+        split8s<sg == 1>(xa, ha, ma, la);
+      }
       split8(xb, hb, mb, lb);
       o[0] = ha; o[2 * SCHP] = ma; o[4 * SCHP] = la;
       o += SIMGP;
@@ -742,60 +972,128 @@ pw_gemm_wgrad_split_kernel(GemmArgs g) {
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  if (T > 0) {
-    fetch(r0);
-    if (T > 1) { fetch(r1); USE_R(r0, 4); } else { USE_R(r0, 0); }
-    split_store(r0, 0, do_rowsum);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-
-  auto step = [&](int t, int cur, Regs& rload, Regs& rsplit) __attribute__((always_inline)) {
-    const u32x4* As = img + cur * 2 * SIMGP + lh * SCHP + wm * 64 + li;
-    const u32x4* Bs = img + (cur * 2 + 1) * SIMGP + lh * SCHP + wn * 64 + li;
-    SplitFrags<NP> f;
-    split_tile_read<NP, 2 * SCHP, 2 * SCHP>(As, Bs, f);
-    __builtin_amdgcn_sched_barrier(0);
-    if (t + 2 < T) { fetch(rload); USE_R(rsplit, 4); }
-    else USE_R(rsplit, 0);
-    // one basic block for every tile; the last tile's split is surplus (stage nobody reads, keep = 0)
-    split_tile_mfma<NP>(f, acc);
-    split_store(rsplit, cur ^ 1, do_rowsum && t + 1 < T);
-    if constexpr (NP > 1) {
-#pragma unroll
-    for (int i = 0; i < (NP == 3 ? 24 : 12); ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);   // five VALU of the two splits
-    }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  };
-  for (int t = 0; t < T; t += 2) {
-    step(t, 0, r0, r1);
-    if (t + 1 < T) step(t + 1, 1, r1, r0);
-  }
-#undef USE_R
-  if (do_rowsum) {
-    rs += __shfl_xor(rs, 1, 64);
-    const int m = m0 + srow;
-    if (sh == 0 && m < g.M) g.rowsum[(int64_t)bz * g.M + m] = rs;
-  }
-  if (slab_flip) {
+  // the prologue, the k-loop and the closing negation of a negated slab: one copy per (sign, row sums)
+  auto run = [&](auto SG, auto RS) __attribute__((always_inline)) {
+    constexpr int sg = decltype(SG)::value, rsm = decltype(RS)::value;
+    const bool rsum = rsm == 2 ? do_rowsum : true;        // (rsm = 0: unused)
+    // (a zero of the copy's own: one shared block of sixteen zeros ahead of the branch reaches later copies through scratch)
+    float zero = 0.f;
+    if constexpr (sg != 2 || rsm != 2) asm volatile("" : "+v"(zero));
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = -acc[i][j][r];
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = zero;
+    // (with several copies, each derives its lane values afresh from the thread index, as the epilogue does: values
+    //  shared between the copies stay live through all of them, beside 168 registers of loop)
+    int ot = tid;
+    if constexpr (sg != 2 || rsm != 2) asm volatile("" : "+v"(ot));
+    const int lwm = (ot >> 7) & 1, lwn = (ot >> 6) & 1, lli = ot & 31, llh = (ot >> 5) & 1;
+    const int srow = ot >> 1, sh = ot & 1;      // the staged row (clamped to the matrix) and k-half
+    u32x4* const o0 = img + sh * SCHP + srow;
+    const float* const Ag = SADDR ? nullptr : g.A + (int64_t)min(m0 + srow, g.M - 1) * g.lda + sh * 8;
+    const float* const Bg = SADDR ? nullptr : g.B + (int64_t)min(n0 + srow, g.N - 1) * g.ldb + sh * 8;
+    const uint32_t voa = ((uint32_t)min(srow, g.M - 1 - m0) * (uint32_t)g.lda + (uint32_t)(sh * 8)) * 4u;      // (host: 128 lda < 2^29)
+    const uint32_t vob = ((uint32_t)min(srow, g.N - 1 - n0) * (uint32_t)g.ldb + (uint32_t)(sh * 8)) * 4u;
+    // (the loads' state and registers belong to the copy: nothing but acc and rs is live where the copies meet)
+    int f_ib = f_ib0, f_kt = f_kt0;
+    const float* sa = sa0;
+    const float* sb = sb0;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    Regs r0{zero4, zero4, zero4, zero4}, r1 = r0;   // defined values: the surplus split of a one-tile range reads r1
+    auto fetch = [&](Regs& r) __attribute__((always_inline)) {
+      if constexpr (SADDR) {
+        asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(r.a0) : "v"(voa), "s"(sa) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=&v"(r.a1) : "v"(voa), "s"(sa) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(r.b0) : "v"(vob), "s"(sb) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=&v"(r.b1) : "v"(vob), "s"(sb) : "memory");
+        sa += SBK; sb += SBK;
+        if (++f_kt == KT) { f_kt = 0; sa += wrap_a; sb += wrap_b; }
+      } else {
+        const float* a = Ag + (int64_t)f_ib * g.a_is + (int64_t)f_kt * SBK;
+        const float* b = Bg + (int64_t)f_ib * g.b_is + (int64_t)f_kt * SBK;
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r.a0) : "v"(a) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=&v"(r.a1) : "v"(a) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(r.b0) : "v"(b) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=&v"(r.b1) : "v"(b) : "memory");
+        if (++f_kt == KT) { f_kt = 0; ++f_ib; }
+      }
+    };
+    if (T > 0) {
+      fetch(r0);
+      if (T > 1) { fetch(r1); USE_R(r0, 4); } else { USE_R(r0, 0); }
+      split_store(SG, RS, r0, o0, 0, rsum);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+    auto step = [&](int t, int cur, Regs& rload, Regs& rsplit) __attribute__((always_inline)) {
+      const u32x4* As = img + cur * 2 * SIMGP + llh * SCHP + lwm * 64 + lli;
+      const u32x4* Bs = img + (cur * 2 + 1) * SIMGP + llh * SCHP + lwn * 64 + lli;
+      SplitFrags<NP> f;
+      split_tile_read<NP, 2 * SCHP, 2 * SCHP>(As, Bs, f);
+      __builtin_amdgcn_sched_barrier(0);
+      if (t + 2 < T) { fetch(rload); USE_R(rsplit, 4); }
+      else USE_R(rsplit, 0);
+      // one basic block for every tile; the last tile's split is surplus (stage nobody reads, keep = 0)
+      split_tile_mfma<NP>(f, acc);
+      split_store(SG, RS, rsplit, o0, cur ^ 1, rsum && t + 1 < T);
+      if constexpr (NP > 1) {
+#pragma unroll
+        for (int i = 0; i < (NP == 3 ? 24 : 12); ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+          __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);   // five VALU of the two splits
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    };
+    for (int t = 0; t < T; t += 2) {
+      step(t, 0, r0, r1);
+      if (t + 1 < T) step(t + 1, 1, r1, r0);
+    }
+    if (sg == 1 || (sg == 2 && slab_flip)) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[i][j][r] = -acc[i][j][r];
+    }
+  };
+  {
+    using std::integral_constant;
+    constexpr integral_constant<int, SIGN_COPIES ? 0 : 2> plain;
+    constexpr integral_constant<int, SIGN_COPIES ? 1 : 2> negated;
+    constexpr integral_constant<int, ROWSUM_COPIES ? 0 : 2> no_sums;
+    constexpr integral_constant<int, ROWSUM_COPIES ? 1 : 2> sums;
+    const bool neg = SIGN_COPIES && slab_flip != 0, with_sums = ROWSUM_COPIES && do_rowsum;      // workgroup-uniform
+    if (with_sums) {
+      if (neg) run(negated, sums); else run(plain, sums);
+    } else {
+      if (neg) run(negated, no_sums); else run(plain, no_sums);
+    }
+  }
+#undef USE_R
+  if (do_rowsum) {
+    int t = tid;
+    if constexpr (SIGN_COPIES || ROWSUM_COPIES) asm volatile("" : "+v"(t));
+    rs += __shfl_xor(rs, 1, 64);
+    const int m = m0 + (t >> 1);
+    if ((t & 1) == 0 && m < g.M) g.rowsum[(int64_t)bz * g.M + m] = rs;
   }
   if constexpr (NP == 2) split_unscale(acc, inv_a, inv_b);
-  gemm_epilogue(g, acc, bz, m0, n0, wm, wn, li, lh);
+  if constexpr (SIGN_COPIES || ROWSUM_COPIES || (NP == 3 && SPLIT_WGRAD_EPILOGUE)) {
+    int t = tid;      // (the epilogue's lane values, derived afresh: see pw_gemm_split_wide_kernel)
+    asm volatile("" : "+v"(t));
+    const int ew = __builtin_amdgcn_readfirstlane((t >> 6) & 3), ewm = ew >> 1, ewn = ew & 1, eli = t & 31, elh = (t >> 5) & 1;
+    // an interior tile of a slab or of dW is a plain store: the straight-line epilogue of the forward kernel, no options
+    if (NP == 3 && SPLIT_WGRAD_EPILOGUE && !g.generic_epilogue && m0 + BM <= g.M && n0 + BN <= g.N)
+      split_epilogue_interior<EP_ON>(g, acc, bz, m0, n0, ewm, ewn, eli, elh);
+    else
+      gemm_epilogue(g, acc, bz, m0, n0, ewm, ewn, eli, elh);
+  } else {
+    gemm_epilogue(g, acc, bz, m0, n0, wm, wn, li, lh);
+  }
 }
 
 // ---- host side: reserve LDS once per device, pick the instantiation, launch -------------------------------------------

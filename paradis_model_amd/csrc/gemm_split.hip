@@ -110,158 +110,6 @@ split_weights_f16_kernel(const float* __restrict__ W, int64_t rs, int64_t cs, in
   }
 }
 
-// ---- the interior-tile epilogue of the fp32-width kernels, one instantiation per option set ---------------------------------
-// gemm_epilogue (gemm_common.h) decides every option at run time and waits for each operand tensor of each group of eight
-// values on its own.  Here the option set EPI is a compile-time bit set (the sets a training step launches: SPLIT_WIDE_EPI
-// below; everything else, ragged tiles included, keeps gemm_epilogue), and per element the operations, their order and
-// their contraction are gemm_epilogue's, so the results are the same bits:
-//   * a wave walks its 64 x 64 block as eight groups (tm, h, tn) of eight rows x 64 lanes; all operand loads of group
-//     g + 1 (map, zmul, res) are issued before the arithmetic and the stores of group g, into the registers the k-loop
-//     has released, and waited for by count (the stores count as well: vmcnt retires in order);
-//   * loads and stores take the saddr form - a scalar row pointer plus ONE 32-bit lane offset ((4 lh ldc + li) x 4 bytes;
-//     the second 32-column tile sits in the instruction's immediate offset) - instead of a 64-bit vector address each;
-//   * bias[m] and sigmoid(gate[m]) are per-row values: lane l of a wave fetches row l of the wave's 64 rows once (one
-//     expf and one division per lane and tile instead of 64), and a pair of groups picks its eight rows with ds_bpermute.
-enum : int { EP_ON = 1, EP_BIAS = 2, EP_MAP = 4, EP_ZOUT = 8, EP_SILU = 16, EP_ZMUL = 32, EP_RES = 64, EP_GATE = 128 };
-
-template <int OFF>
-__device__ __forceinline__ void ep_load(float& x, uint32_t voff, const float* p) {
-  asm volatile("global_load_dword %0, %1, %2 offset:%3" : "=&v"(x) : "v"(voff), "s"(p), "n"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void ep_store(float x, uint32_t voff, float* p) {
-  asm volatile("global_store_dword %0, %1, %2 offset:%3" :: "v"(voff), "v"(x), "s"(p), "n"(OFF) : "memory");
-}
-// at most N younger vector-memory operations outstanding; the registers waited for are INPUTS (see USE_X below)
-template <int N>
-__device__ __forceinline__ void ep_wait(const float (&a)[8]) {
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]),
-               "v"(a[7]) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void ep_wait(const float (&a)[8], const float (&b)[8]) {
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]),
-               "v"(a[7]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]), "v"(b[6]), "v"(b[7]) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void ep_wait(float a, float b) {
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N), "v"(a), "v"(b) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ float ep_row(float rowvec, int addr) {      // rowvec of lane addr / 4
-  return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(rowvec)));
-}
-template <class T>
-__device__ __forceinline__ T* ep_uniform(T* p) {      // wave-uniform by construction: pin it to scalar registers
-  const uint64_t a = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  return reinterpret_cast<T*>(((uint64_t)hi << 32) | lo);
-}
-
-template <int EPI>
-__device__ __forceinline__ void split_epilogue_interior(const GemmArgs& g, f32x16 (&acc)[2][2], int bz, int m0, int n0,
-                                                        int wm, int wn, int li, int lh) {
-  constexpr bool BIAS = EPI & EP_BIAS, MAP = EPI & EP_MAP, ZOUT = EPI & EP_ZOUT, SILU = EPI & EP_SILU, ZMUL = EPI & EP_ZMUL,
-                 RES = EPI & EP_RES, GATE = EPI & EP_GATE;
-  static_assert(!(GATE && !RES) && !(ZMUL && (SILU || ZOUT)), "no such epilogue");
-  // operand tensors of a group, their slots in the load buffers, loads / stores per group
-  constexpr int NT = MAP + ZMUL + RES, I_MAP = 0, I_ZM = MAP, I_RES = MAP + ZMUL;
-  static_assert(NT <= 2, "a third operand tensor needs a third ep_wait");
-  constexpr int L = 8 * NT, S = 8 * (1 + ZOUT);
-  const int wrow = __builtin_amdgcn_readfirstlane(m0 + wm * 64), wcol = __builtin_amdgcn_readfirstlane(n0 + wn * 64);
-  const int64_t ld = g.ldc, tile = (int64_t)wrow * ld + wcol;
-  float* const Cs = ep_uniform(g.C + (int64_t)bz * g.c_bs + tile);
-  float* const zos = ZOUT ? ep_uniform(g.zout + (int64_t)bz * g.zout_bs + tile) : nullptr;
-  const float* const mps = MAP ? ep_uniform(g.map + tile) : nullptr;
-  const float* const zms = ZMUL ? ep_uniform(g.zmul + (int64_t)bz * g.zmul_bs + tile) : nullptr;
-  const float* const rss = RES ? ep_uniform(g.res + (int64_t)bz * g.res_bs + tile) : nullptr;
-  const uint32_t voff = ((uint32_t)(4 * lh) * (uint32_t)ld + (uint32_t)li) * 4u;      // (host: ldc < 2^26)
-  const int radr = 16 * lh;                                   // ds_bpermute address of row 4 lh of the wave's 64
-  // group gi = (tm, h, tn); element q sits in row tm 32 + (q & 3) + 8 (2 h + (q >> 2)) (+ 4 lh) of the wave's block
-  auto rowof = [](int gi, int q) constexpr { return (gi >> 2) * 32 + (q & 3) + 8 * (2 * ((gi >> 1) & 1) + (q >> 2)); };
-
-  float bv = 0.f, gv = 0.f;             // lane l: bias / gate of row wrow + l
-  float buf[2][NT ? NT : 1][8];
-  auto issue = [&](auto G) __attribute__((always_inline)) {
-    constexpr int gi = decltype(G)::value, OFF = (gi & 1) * 128;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int64_t ro = (int64_t)rowof(gi, q) * ld;
-      if constexpr (MAP) ep_load<OFF>(buf[gi & 1][I_MAP][q], voff, mps + ro);
-      if constexpr (ZMUL) ep_load<OFF>(buf[gi & 1][I_ZM][q], voff, zms + ro);
-      if constexpr (RES) ep_load<OFF>(buf[gi & 1][I_RES][q], voff, rss + ro);
-    }
-  };
-  float br[8], gr[8];                   // the rows of the current (tm, h): picked at tn = 0, used by both column tiles
-  if constexpr (BIAS) ep_load<0>(bv, (uint32_t)(32 * lh + li) * 4u, ep_uniform(g.bias + wrow));
-  if constexpr (GATE) ep_load<0>(gv, (uint32_t)(32 * lh + li) * 4u, ep_uniform(g.gate + wrow));
-  if constexpr (NT > 0) issue(std::integral_constant<int, 0>{});
-  __builtin_amdgcn_sched_barrier(0);
-
-  auto group = [&](auto G) __attribute__((always_inline)) {
-    constexpr int gi = decltype(G)::value, tm = gi >> 2, h = (gi >> 1) & 1, tn = gi & 1, OFF = tn * 128, b = gi & 1;
-    if constexpr (NT > 0 && gi < 7) {
-      issue(std::integral_constant<int, gi + 1>{});
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (gi == 0 && (BIAS || GATE)) {
-      ep_wait<NT ? 2 * L : 0>(bv, gv);       // younger: the loads of groups 0 and 1
-      if constexpr (GATE) gv = gate_sigmoid(gv);
-    }
-    if constexpr (tn == 0 && (BIAS || GATE)) {      // eight (sixteen) picks back to back, one counted LDS wait each
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        if constexpr (BIAS) br[q] = ep_row(bv, radr + 4 * rowof(gi, q));
-        if constexpr (GATE) gr[q] = ep_row(gv, radr + 4 * rowof(gi, q));
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // younger than this group's loads: the stores of the group before, the loads of the group after
-    constexpr int YOUNGER = (gi < 7 ? L : 0) + (gi > 0 ? S : 0);
-    if constexpr (NT == 1) ep_wait<YOUNGER>(buf[b][0]);
-    if constexpr (NT == 2) ep_wait<YOUNGER>(buf[b][0], buf[b][1]);
-    float v[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) v[q] = acc[tm][tn][8 * h + q];
-    if constexpr (BIAS) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] += br[q];
-    }
-    if constexpr (MAP) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] += buf[b][I_MAP][q];
-    }
-    if constexpr (ZOUT) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) ep_store<OFF>(v[q], voff, zos + (int64_t)rowof(gi, q) * ld);
-    }
-    if constexpr (ZMUL) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] *= act_grad(buf[b][I_ZM][q], PARADIS_ACT_SILU);
-    } else if constexpr (SILU) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = act_apply(v[q], PARADIS_ACT_SILU);
-    }
-    if constexpr (RES) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float r = buf[b][I_RES][q];
-        if constexpr (GATE) v[q] = fmaf(gr[q], v[q] - r, r);
-        else v[q] += r;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) ep_store<OFF>(v[q], voff, Cs + (int64_t)rowof(gi, q) * ld);
-    __builtin_amdgcn_sched_barrier(0);      // (a group's arithmetic stays behind the stores of the group before)
-  };
-  group(std::integral_constant<int, 0>{}); group(std::integral_constant<int, 1>{});
-  group(std::integral_constant<int, 2>{}); group(std::integral_constant<int, 3>{});
-  group(std::integral_constant<int, 4>{}); group(std::integral_constant<int, 5>{});
-  group(std::integral_constant<int, 6>{}); group(std::integral_constant<int, 7>{});
-}
-
 // fwd / dgrad:  C_b = epi( A . B_b ),  A = split weight image (g.A, batch stride g.a_bs chunks),
 // B_b[K,N] fp32 with n contiguous.
 //
@@ -453,7 +301,12 @@ pw_gemm_split_wide_kernel(GemmArgs g) {
     const int q = nwg >> 3, r = nwg & 7, xcd = id & 7;
     L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
   }
-  const int mt = L % MT, nt2 = (L / MT) % NT2, bz = L / (MT * NT2);
+  int mt = L % MT, nt2 = (L / MT) % NT2, bz = L / (MT * NT2);
+  if constexpr (NP == 3 && SPLIT_SIGN_LOOPS_FWD && SPLIT_SIGNED) {
+    // (uniform, but divided on the vector unit: with two loop copies the epilogue's copies of these no longer fit into
+    //  the 128 vector registers beside the loops - they belong in scalar registers)
+    mt = __builtin_amdgcn_readfirstlane(mt); nt2 = __builtin_amdgcn_readfirstlane(nt2); bz = __builtin_amdgcn_readfirstlane(bz);
+  }
   const bool live = NSUB * nt2 + sub < NT;           // wave-uniform
   const int nt = min(NSUB * nt2 + sub, NT - 1);
   const int m0 = mt * BM, n0 = nt * BN;
@@ -491,22 +344,28 @@ pw_gemm_split_wide_kernel(GemmArgs g) {
 
   const uint32_t flip = split_flip_mask(ltid & 127);
   if constexpr (NP == 2) sc_b = __uint_as_float(__float_as_uint(sc_b) ^ flip);
-  float xb[2][8] = {};     // defined values: the surplus split of the last tile reads a set that was never loaded
   auto issueA = [&](int t) __attribute__((always_inline)) {
     if (doA)
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(Ag + (int64_t)t * SIMG), (lds_ptr_t)(img + (2 * NSUB + t % SA) * SIMG + wave * 64), 16, 0, 0);
     if (doA2)
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(Ag + (int64_t)t * SIMG + 512), (lds_ptr_t)(img + (2 * NSUB + t % SA) * SIMG + 512 + wave * 64), 16, 0, 0);
   };
-  auto split_store = [&](const float (&x)[8], u32x4* o) __attribute__((always_inline)) {
+  // SG: the sign mode of the loop copy that calls - 0 / 1 = plain / negated at compile time, 2 = the run-time mask
+  auto split_store = [&](auto SG, const float (&x)[8], u32x4* o) __attribute__((always_inline)) {
+    constexpr int sg = decltype(SG)::value;
     if constexpr (NP == 3) {
       u32x4 h, m, l;
-      // sign checkerboard: odd 64-column blocks are staged negated.  (Two code paths behind a wave-uniform branch
-      // with the sign folded into source modifiers - no v_xor - measured SLOWER, 154.8 against 153.0 ms per step: the
-      // branch takes the split out of the MFMA block's schedule.)
-      float xs[8];
-      flip8(xs, x, flip);
-      split8(xs, h, m, l);
+      // sign checkerboard: odd 64-column blocks are staged negated.  (Two code paths behind a wave-uniform branch INSIDE
+      // the step, with the sign folded into source modifiers - no v_xor - measured SLOWER, 154.8 against 153.0 ms per
+      // step: the branch takes the split out of the MFMA block's schedule.  Two copies of the WHOLE loop keep one block per
+      // step and measured 1.3 ms faster per step than the v_xor loop: profiles/r08_gemm_sign_loops.txt.)
+      if constexpr (sg == 2) {
+        float xs[8];
+        flip8(xs, x, flip);
+        split8(xs, h, m, l);
+      } else {
+        split8s<sg == 1>(x, h, m, l);
+      }
       o[0] = h; o[2 * SCH] = m; o[4 * SCH] = l;
     } else {
       u32x4 h, l;
@@ -531,85 +390,100 @@ pw_gemm_split_wide_kernel(GemmArgs g) {
   u32x4* const Bst = img + sub * 2 * SIMG + bh * SCH + (ltid & 127);   // this thread's chunk in its sub's stage 0
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  for (int u = 0; u < DA && u < T; ++u) issueA(u);
-  fetchB(0, xb[0]);
-  USE_X(xb[0], 0);
-  if (T > 1) fetchB(1, xb[1]);
-  split_store(xb[0], Bst);
-  if (T > 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  auto step = [&](int t, int cur, float (&xload)[8], float (&xsplit)[8]) __attribute__((always_inline)) {
-    const u32x4* As = img + (2 * NSUB + t % SA) * SIMG + lh * SCH + wm * 64 + li;
-    const u32x4* Bs = img + (sub * 2 + cur) * SIMG + lh * SCH + wn * 64 + li;
-    const bool dmaA = t + DA < T, ldB = t + 2 < T;
-    if (dmaA) issueA(t + DA);
-    if (ldB) fetchB(t + 2, xload);
-    // xsplit (tile t+1) was loaded a step ago; younger operations: this step's DMA piece(s) and 8 loads
-    if (dmaA && ldB && doA2) USE_X(xsplit, 10);
-    else if (dmaA && ldB && doA) USE_X(xsplit, 9);
-    else if (ldB) USE_X(xsplit, 8);
-    else USE_X(xsplit, 0);
-    if constexpr (NP == 3) {
-      // three planes at 128 registers: the B fragments of ONE plane at a time (8 registers instead of 24), planes
-      // in the order l, m, h so that the products still arrive roughly smallest first:
-      //   ah.bl | am.bm, ah.bm | al.bh, am.bh, ah.bh
-      auto mfma_block = [&]() __attribute__((always_inline)) {
-        u32x4 a[3][2], b[2];
+  // the prologue and the k-loop: one copy per sign mode (the activation registers belong to the copy: nothing but acc is
+  // live where the copies meet)
+  auto run = [&](auto SG) __attribute__((always_inline)) {
+    // (a zero of the copy's own: one shared block of sixteen zeros ahead of the branch reaches the second copy through scratch)
+    float zero = 0.f;
+    if constexpr (decltype(SG)::value != 2) asm volatile("" : "+v"(zero));
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) { a[pl][0] = As[pl * 2 * SCH]; a[pl][1] = As[pl * 2 * SCH + 32]; }
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int pb = 2; pb >= 0; --pb) {
-          b[0] = Bs[pb * 2 * SCH]; b[1] = Bs[pb * 2 * SCH + 32];
+      for (int j = 0; j < 2; ++j)
 #pragma unroll
-          for (int pa = 2 - pb; pa >= 0; --pa)
-#pragma unroll
-            for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-              for (int tn = 0; tn < 2; ++tn) SPLIT_MFMA(a[pa][tm], b[tn], acc[tm][tn]);
-        }
-      };
-#if SPLIT_STAGGER
-      // SIMD partners out of phase (MI355X_MICROARCH.md, two waves per SIMD, item 9): waves 4-7 (sub 1) split and store
-      // tile t+1 FIRST and multiply afterwards, waves 0-3 the other way round - one half of a SIMD's waves is on the
-      // vector unit and the LDS store path while the other half feeds the matrix pipe
-      // (ONE copy of the MFMA block: a second copy behind the branch spills the accumulators)
-      if (sub == 1) split_store(xsplit, Bst + (cur ^ 1) * SIMG);
-      __builtin_amdgcn_sched_barrier(0);
-      mfma_block();
-      __builtin_amdgcn_sched_barrier(0);
-      if (sub == 0) split_store(xsplit, Bst + (cur ^ 1) * SIMG);
-#else
-      mfma_block();
-      split_store(xsplit, Bst + (cur ^ 1) * SIMG);
-#endif
-      // (no sched_group_barrier pinning here: the 1 MFMA : 3 VALU pattern of the 128 x 128 kernel measured 0.7 % slower
-      //  on the step than the compiler's own order, three rounds on one box)
-    } else {
-      SplitFrags<NP> f;
-      split_tile_read<NP, 2 * SCH, 2 * SCH>(As, Bs, f);
-      split_tile_mfma<NP>(f, acc);
-      split_store(xsplit, Bst + (cur ^ 1) * SIMG);
-      __builtin_amdgcn_sched_group_barrier(0x100, 4 * NP, 0);   // all fragment reads first, in first-use order
-#pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-      }
-    }
-    // weight tile t+1 landed (8 loads of this step are younger), own ds_writes done, the loads of t+2 in flight
-    if (dmaA && ldB) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = zero;
+    float xb[2][8] = {};     // defined values: the surplus split of the last tile reads a set that was never loaded
+    for (int u = 0; u < DA && u < T; ++u) issueA(u);
+    fetchB(0, xb[0]);
+    USE_X(xb[0], 0);
+    if (T > 1) fetchB(1, xb[1]);
+    split_store(SG, xb[0], Bst);
+    if (T > 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    auto step = [&](int t, int cur, float (&xload)[8], float (&xsplit)[8]) __attribute__((always_inline)) {
+      const u32x4* As = img + (2 * NSUB + t % SA) * SIMG + lh * SCH + wm * 64 + li;
+      const u32x4* Bs = img + (sub * 2 + cur) * SIMG + lh * SCH + wn * 64 + li;
+      const bool dmaA = t + DA < T, ldB = t + 2 < T;
+      if (dmaA) issueA(t + DA);
+      if (ldB) fetchB(t + 2, xload);
+      // xsplit (tile t+1) was loaded a step ago; younger operations: this step's DMA piece(s) and 8 loads
+      if (dmaA && ldB && doA2) USE_X(xsplit, 10);
+      else if (dmaA && ldB && doA) USE_X(xsplit, 9);
+      else if (ldB) USE_X(xsplit, 8);
+      else USE_X(xsplit, 0);
+      if constexpr (NP == 3) {
+        // three planes at 128 registers: the B fragments of ONE plane at a time (8 registers instead of 24), planes
+        // in the order l, m, h so that the products still arrive roughly smallest first:
+        //   ah.bl | am.bm, ah.bm | al.bh, am.bh, ah.bh
+        auto mfma_block = [&]() __attribute__((always_inline)) {
+          u32x4 a[3][2], b[2];
+#pragma unroll
+          for (int pl = 0; pl < 3; ++pl) { a[pl][0] = As[pl * 2 * SCH]; a[pl][1] = As[pl * 2 * SCH + 32]; }
+#pragma unroll
+          for (int pb = 2; pb >= 0; --pb) {
+            b[0] = Bs[pb * 2 * SCH]; b[1] = Bs[pb * 2 * SCH + 32];
+#pragma unroll
+            for (int pa = 2 - pb; pa >= 0; --pa)
+#pragma unroll
+              for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn) SPLIT_MFMA(a[pa][tm], b[tn], acc[tm][tn]);
+          }
+        };
+#if SPLIT_STAGGER
+        // SIMD partners out of phase (MI355X_MICROARCH.md, two waves per SIMD, item 9): waves 4-7 (sub 1) split and store
+        // tile t+1 FIRST and multiply afterwards, waves 0-3 the other way round - one half of a SIMD's waves is on the
+        // vector unit and the LDS store path while the other half feeds the matrix pipe
+        // (ONE copy of the MFMA block: a second copy behind the branch spills the accumulators)
+        if (sub == 1) split_store(SG, xsplit, Bst + (cur ^ 1) * SIMG);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_block();
+        __builtin_amdgcn_sched_barrier(0);
+        if (sub == 0) split_store(SG, xsplit, Bst + (cur ^ 1) * SIMG);
+#else
+        mfma_block();
+        split_store(SG, xsplit, Bst + (cur ^ 1) * SIMG);
+#endif
+        // (no sched_group_barrier pinning here: the 1 MFMA : 3 VALU pattern of the 128 x 128 kernel measured 0.7 % slower
+        //  on the step than the compiler's own order, three rounds on one box)
+      } else {
+        SplitFrags<NP> f;
+        split_tile_read<NP, 2 * SCH, 2 * SCH>(As, Bs, f);
+        split_tile_mfma<NP>(f, acc);
+        split_store(SG, xsplit, Bst + (cur ^ 1) * SIMG);
+        __builtin_amdgcn_sched_group_barrier(0x100, 4 * NP, 0);   // all fragment reads first, in first-use order
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        }
+      }
+      // weight tile t+1 landed (8 loads of this step are younger), own ds_writes done, the loads of t+2 in flight
+      if (dmaA && ldB) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    };
+    for (int t = 0; t < T; t += 2) {
+      step(t, 0, xb[0], xb[1]);
+      if (t + 1 < T) step(t + 1, 1, xb[1], xb[0]);
+    }
   };
-  for (int t = 0; t < T; t += 2) {
-    step(t, 0, xb[0], xb[1]);
-    if (t + 1 < T) step(t + 1, 1, xb[1], xb[0]);
+  if constexpr (NP == 3 && SPLIT_SIGN_LOOPS_FWD && SPLIT_SIGNED) {
+    // the wave's column-block bit (= wn), chosen once: both copies issue the same barriers per step
+    if (__builtin_amdgcn_readfirstlane((ltid >> 6) & 1)) run(std::integral_constant<int, 1>{});
+    else run(std::integral_constant<int, 0>{});
+  } else {
+    run(std::integral_constant<int, 2>{});
   }
 #undef USE_X
   if (live) {
@@ -676,8 +550,10 @@ constexpr int SPLIT_WIDE_NSUB = 2;
 constexpr GemmKernelEntry SPLIT[2] = {{&pw_gemm_split_kernel<2>, split_lds(2)}, {&pw_gemm_split_kernel<3>, split_lds(3)}};
 constexpr GemmKernelEntry SPLIT_WIDE[2] = {{&pw_gemm_split_wide_kernel<SPLIT_WIDE_NSUB, 2>, split_wide_lds(SPLIT_WIDE_NSUB, 2)},
                                            {&pw_gemm_split_wide_kernel<SPLIT_WIDE_NSUB, 3>, split_wide_lds(SPLIT_WIDE_NSUB, 3)}};
-constexpr GemmKernelEntry SPLIT_WGRAD[2] = {{&pw_gemm_wgrad_split_kernel<2>, split_lds_wgrad(2)},
-                                            {&pw_gemm_wgrad_split_kernel<3>, split_lds_wgrad(3)}};
+// ([2]: bf16x3 with scalar-base loads, split_wgrad_a32)
+constexpr GemmKernelEntry SPLIT_WGRAD[3] = {{&pw_gemm_wgrad_split_kernel<2>, split_lds_wgrad(2)},
+                                            {&pw_gemm_wgrad_split_kernel<3>, split_lds_wgrad(3)},
+                                            {&pw_gemm_wgrad_split_kernel<3, 1>, split_lds_wgrad(3)}};
 // bf16x3 on the 128 x 256 tile with a compile-time epilogue: the option sets the default model's training step launches
 // (DESIGN.md 4.1), SPLIT_WIDE_EPI_SETS[i] = the set of SPLIT_WIDE_EPI[i].  Any other set runs SPLIT_WIDE.
 #define EPI_SETS(X)                                                                                                       \
@@ -799,9 +675,22 @@ int pd_split_launch(const GemmArgs& d, int scheme, hipStream_t st) {
   return launch_entry(SPLIT, np - 2, once, "pw_gemm(split)", MT * NT * d.nbatch, 256, st, d);
 }
 
+// pw_gemm_wgrad_split_kernel<3, 1> adds an unsigned 32-bit BYTE offset to the pointer of a tile's first row: the last
+// access of a tile ends (127 ld + 16) x 4 bytes behind it, below 2^31 for ld < 2^22.  Leading dimensions from 2^22 floats
+// on (16 MiB rows) take <3, 0>, today's 64-bit vector addresses; neither that fallback nor the ldc >= 2^26 generic
+// epilogue is reached by a test - an operand of such rows is tens of GiB.
+bool split_wgrad_a32(const GemmArgs& g) {
+  constexpr int64_t LIM = (int64_t)1 << 22;
+  return SPLIT_WGRAD_SADDR && g.lda >= 0 && g.lda < LIM && g.ldb >= 0 && g.ldb < LIM;
+}
+
 int pd_split_launch_wgrad(const GemmArgs& g, const WgradPlan& p, hipStream_t st) {
   static PerDeviceOnce once;
-  return launch_entry(SPLIT_WGRAD, p.kind == WgradKind::F16x2 ? 0 : 1, once, "pw_gemm_wgrad(split)", p.grid, p.block, st, g, p.lds);
+  if (p.kind == WgradKind::F16x2) return launch_entry(SPLIT_WGRAD, 0, once, "pw_gemm_wgrad(split)", p.grid, p.block, st, g, p.lds);
+  GemmArgs d = g;
+  const char* e = getenv("PARADIS_GEMM_EPILOGUE");      // (read at every launch, as split_epilogue_flags does)
+  d.generic_epilogue = (e && strcmp(e, "generic") == 0) || d.ldc >= (1 << 26);
+  return launch_entry(SPLIT_WGRAD, split_wgrad_a32(d) ? 2 : 1, once, "pw_gemm_wgrad(split)", p.grid, p.block, st, d, p.lds);
 }
 
 int64_t pd_split_image_chunks(int M, int K, int np) { return split_image_chunks(M, K, np); }
